@@ -1,18 +1,23 @@
 """Hot-path bench: rays/sec of the per-ray renderer on synthetic Balloon1-shaped inputs (BASELINE.json configs[1]).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one pass of the static-branch hot path over one batch of R = 4096 rays per GPU (64 coarse samples, 8 source
 views): sample_along_ray -> project_gather -> DynibarStatic (views / points / blend kernels) -> composite, all through the
 C-ABI of libdynibar_hip.so with inputs resident in HBM.  With N > 1 every rank renders its own tile of rays (weak scaling: rays
 are independent) and each step ends with the RCCL all-gather of the rendered pixels.
-Prints ONE JSON line (rank 0).  The CPU leg times the oracle (the reference algorithm restated on torch-CPU) on a bounded
+Prints ONE JSON line (rank 0).  A plain run only sets up, warms up, times the K steps (`ms_per_step`, `value`, and the rooflines
+priced from the per-kernel clocks of those same steps), writes the last step's outputs if `--dump-outputs DIR` is given (DIR/<name>.npy,
+float32: the composite's arrays of rank 0, plus the all-gathered pixels with N > 1; the inputs are seeded, so two builds can be
+compared output for output) and prints the line.  Everything below takes runs of its own and is measured with `--full` only.
+The CPU leg times the oracle (the reference algorithm restated on torch-CPU) on a bounded
 sample of the same workload (median of 3); it is a reported baseline, not the target.  Extra legs in the same line (`extra`): the
 same step at the Nvidia eval's real static view count (11), one full 288x512 frame through render_single_image_nvi (on N > 1 GPUs:
 ray-tiled across the ranks -- a strong-scaling number next to the weak-scaling headline), and the HBM traffic of the network and
-gather kernels measured by rocprofv3 --pmc children of this same command.  With N > 1 the line also carries every rank's own ms per step, the
-cost of the pixel all-gather alone and, for the frame leg, every rank's render and gather times.
+gather kernels measured by rocprofv3 --pmc children of this same command.  With N > 1 the line also carries every rank's own ms per step and,
+with --full, the RCCL readiness checks made before timing, the cost of the pixel all-gather alone and, for the frame leg, every rank's render and
+gather times.
 `--dry-run` rehearses exactly this control flow on CPU ranks over gloo with a stub of the kernel layer (tests/test_bench_dry_run.py launches it
 through torch.distributed.run with 2 ranks): the product has no CPU path, so the numbers of a dry run mean nothing -- the point is that the
 N > 1 command cannot fail on first contact with an 8-GPU node for a reason a CPU could have found.
@@ -131,6 +136,26 @@ class DryFrameCase:
   def render(self, smp, rb):
     return self.RI.render_single_image_nvi((0, None), (None, None), ([0], None), smp, rb, None, None, self.chunk, 4, self.args, N_importance=4, det=True,
                                            is_train=False)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, out, gathered=None):
+  """--dump-outputs: every tensor of the last timed step's output dict (and the all-gathered pixels of all ranks) as d/<name>.npy in float32.  An
+  output set above 64 MB is cut to the same fixed, seeded sample of rows in every array (sorted row indices, numpy seed 0)."""
+  arrays = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+  if gathered is not None:
+    arrays['gathered_pixels'] = gathered
+  arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+  total = sum(v.nbytes for v in arrays.values())
+  os.makedirs(d, exist_ok=True)
+  for k, v in arrays.items():
+    if total > DUMP_LIMIT_BYTES and v.ndim > 0:
+      n = v.shape[0]
+      keep = max(1, int(n * DUMP_LIMIT_BYTES // total))
+      v = v[np.sort(np.random.default_rng(0).choice(n, keep, replace=False))]
+    np.save(os.path.join(d, k + '.npy'), np.ascontiguousarray(v))
 
 
 def timed(lib, step, steps, warmup, fence):
@@ -281,10 +306,16 @@ def main():
                   'multi-rank code path -- per-step pixel all-gather, barrier-bracketed fences, the ray-tiled frame leg -- so that this path runs on a single MI355X')
   ap.add_argument('--gather', choices=('torch', 'abi'), default=None, help="the frame leg's pixel gather: torch.distributed (default) or the C-ABI's dyn_gather_tiles")
   ap.add_argument('--frame-only', action='store_true', help='of the extra legs only the full frame (tests)')
+  ap.add_argument('--full', action='store_true', help='also run every leg beyond the headline (CPU baseline and oracle check, the 6-term engine, the extra '
+                  'legs, the rocprofv3 --pmc children, the N > 1 readiness checks and all-gather cost); the --no-* / --cpu-rays / --frame-only options '
+                  'select among them')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write the timed path's outputs of the last timed step as DIR/<name>.npy (float32)")
   ap.add_argument('--dump-rgb', default=None, help=argparse.SUPPRESS)  # (child of the x6 leg: the last step's colours of the first cpu-rays rays as .npy)
   ap.add_argument('--child', nargs='?', const='plain', default=None, help=argparse.SUPPRESS)  # 'plain': no baseline / extra legs; 'check': keep the oracle check (x6 leg)
   a = ap.parse_args()
   a.x6 = not a.no_x6
+  if not a.full:  # a plain run: set up, warm up, time the steps, dump, print the line
+    a.cpu_rays, a.no_extra, a.no_traffic, a.x6 = 0, True, True, False
   if a.child:
     a.cpu_rays, a.no_extra, a.no_traffic, a.x6 = 0 if a.child == 'plain' else a.cpu_rays, True, True, False
   if a.dry_run:
@@ -324,7 +355,7 @@ def main():
 
   # ---- N > 1 readiness, BEFORE anything is timed: does RCCL see all N ranks, through torch.distributed and through the package's own communicator? ----
   readiness = None
-  if multi_rank:
+  if multi_rank and a.full:
     readiness = {'world_size': world, 'backend': dist.get_backend()}
     names = [None] * world
     dist.all_gather_object(names, 'cpu (dry run)' if dry else '%s #%d' % (torch.cuda.get_device_name(dev), local_rank))
@@ -398,17 +429,21 @@ def main():
 
   out, dt_own, kernels = timed(lib, step, a.steps, a.warmup, fence)
   dt = max_over_ranks(dt_own)
+  if a.dump_outputs and rank == 0:
+    dump_outputs(a.dump_outputs, out, gathered)
   multi = None
   if multi_rank:
-    # what the collective alone costs (the same payload, the same stream, nothing to overlap with), and every rank's own clock
+    # every rank's own clock, and (--full) what the collective alone costs (the same payload, the same stream, nothing to overlap with)
     send = pixels(out).contiguous()
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-      dist.all_gather_into_tensor(gathered, send)
-    fence()
-    ag = max_over_ranks(time.perf_counter() - t0)
-    multi = {'per_rank_ms_per_step': [round(v / a.steps * 1e3, 4) for v in every_rank(dt_own)], 'allgather_alone_ms_per_step': ag / a.steps * 1e3,
+    ag = None
+    if a.full:
+      fence()
+      t0 = time.perf_counter()
+      for _ in range(a.steps):
+        dist.all_gather_into_tensor(gathered, send)
+      fence()
+      ag = max_over_ranks(time.perf_counter() - t0) / a.steps * 1e3
+    multi = {'per_rank_ms_per_step': [round(v / a.steps * 1e3, 4) for v in every_rank(dt_own)], 'allgather_alone_ms_per_step': ag,
              'allgather_bytes_per_rank_per_step': int(send.numel() * 4), 'backend': dist.get_backend(), 'readiness': readiness,
              'rccl_ranks': (readiness or {}).get('rccl_ranks'), 'devices': (readiness or {}).get('devices')}
 

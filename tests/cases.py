@@ -234,3 +234,46 @@ def grad_digest(g, seed=5):
 
 MONO_TRAIN_LOSSES = {'full': ('rgb', 'disp', 'flow', 'cycle', 'reg', 'entropy', 'distortion', 'static'), 'flow': ('flow',), 'cycle': ('cycle',),
                      'reg': ('reg',), 'rgb': ('rgb',)}
+
+
+CRITERION_SEEDS = (0, 1)
+
+
+def criterion_cases(m, seed, R=37, V=3):
+  """The loss helpers train.py imports, on seeded inputs: [(name, loss of module m, leaves)] (tests/test_criterion.py and its golden,
+  tests/golden/criterion.npz).  m: dynibar_amd.criterion or the reference's ibrnet/criterion.py."""
+  g = torch.Generator().manual_seed(seed)
+  r = lambda *s: torch.rand(*s, generator=g, dtype=torch.float32)
+  outputs = dict(rgb=r(R, 3).requires_grad_(), mask=(r(R) > 0.2), occ_weight_map=r(R).requires_grad_())
+  batch = dict(rgb=r(R, 3))
+  mm, flow, gt_flow, gt_mask = (r(R) > 0.3).float(), r(V, R, 2).requires_grad_(), r(V, R, 2), (r(V, R, 1) > 0.4).float()
+  return [
+      ('Criterion', lambda: m.Criterion()(outputs, batch), [outputs['rgb']]),
+      ('Criterion+motion_mask', lambda: m.Criterion()(outputs, batch, mm), [outputs['rgb']]),
+      ('temporal_rgb', lambda: m.compute_temporal_rgb_loss(outputs, batch, mm), [outputs['rgb'], outputs['occ_weight_map']]),
+      ('temporal_rgb no mask', lambda: m.compute_temporal_rgb_loss(outputs, batch), [outputs['rgb'], outputs['occ_weight_map']]),
+      ('rgb', lambda: m.compute_rgb_loss(outputs['rgb'], batch, outputs['mask'].float()), [outputs['rgb']]),
+      ('entropy', lambda: m.compute_entropy(outputs['occ_weight_map']), [outputs['occ_weight_map']]),
+      ('flow', lambda: m.compute_flow_loss(flow, gt_flow, gt_mask), [flow]),
+  ]
+
+
+# the reference's argument sets (tests/test_model_adapter.py) and the module constructions whose structure tests/golden/reference_modules.json records
+MODULE_ARG_SETS = {'nvidia_eval': dict(anti_alias_pooling=1, mask_rgb=0), 'kid_running': dict(anti_alias_pooling=0, mask_rgb=1)}
+MODULE_ATTRS = ('anti_alias_pooling', 'mask_rgb', 'shift', 'sf_mag_div', 'num_basis')
+
+
+def load_golden(golden_dir, name):
+  """tests/golden/<name> as a dict of arrays; a golden stored in parts (<stem>.part<i>.npz, tests/golden/make_golden.py:save_parts) is merged."""
+  import glob
+  import os
+  path = os.path.join(golden_dir, name)
+  if os.path.exists(path):
+    return dict(np.load(path))
+  stem = path[:-len('.npz')] if path.endswith('.npz') else path
+  parts = sorted(glob.glob(stem + '.part*.npz'), key=lambda p: int(p[len(stem) + len('.part'):-len('.npz')]))
+  assert parts, f'no golden {name} in {golden_dir}'
+  out = {}
+  for p in parts:
+    out.update(np.load(p))
+  return out

@@ -33,6 +33,25 @@ def npy(x):
   return np.asarray(x)
 
 
+def save_parts(stem, out, limit=900 << 10):
+  """A golden too large for one committed file: <stem>.part<i>.npz, each about `limit` compressed bytes at most, arrays in their order
+  (cases.load_golden merges them back)."""
+  import glob
+  import zlib
+  for f in glob.glob(os.path.join(HERE, stem + '.npz')) + glob.glob(os.path.join(HERE, stem + '.part*.npz')):
+    os.remove(f)
+  parts, cur, size = [], {}, 0
+  for k, v in out.items():
+    n = len(zlib.compress(np.ascontiguousarray(v).tobytes()))
+    if cur and size + n > limit:
+      parts.append(cur)
+      cur, size = {}, 0
+    cur[k], size = v, size + n
+  parts.append(cur)
+  for i, p in enumerate(parts):
+    np.savez_compressed(os.path.join(HERE, f'{stem}.part{i + 1}.npz'), **p)
+
+
 def flat(prefix, d, out):
   for k, v in d.items():
     if v is None:
@@ -300,7 +319,7 @@ def image_mono_train_goldens():
         elif isinstance(v, list):
           for i, t in enumerate(v):
             out[f'{grp}/{k}#{i}'] = npy(t)
-  np.savez_compressed(os.path.join(HERE, 'image_mono_train.npz'), **out)
+  save_parts('image_mono_train', out)
   print('image_mono_train', len(out), 'arrays')
 
 
@@ -386,7 +405,7 @@ def train_static_goldens():
     for k, p in model.net_coarse_st.named_parameters():
       out[tag + 'grad/' + k] = npy(p.grad)
     assert all(p.grad is None for p in model.net_coarse_dy.parameters())
-  np.savez_compressed(os.path.join(HERE, 'train_static.npz'), **out)
+  save_parts('train_static', out)
   print('train_static', len(out), 'arrays', sum(v.nbytes for v in out.values()) // 1024, 'KiB')
 
 
@@ -524,8 +543,65 @@ def camera_format_goldens():
   print('camera_format', len(out), 'arrays', sum(v.nbytes for v in out.values()) // 1024, 'KiB')
 
 
+def criterion_goldens():
+  """The reference's loss helpers (ibrnet/criterion.py + utils.img2charbonier) on the seeded inputs of cases.criterion_cases: every value and
+  every gradient with respect to the case's leaves."""
+  import importlib
+  # utils.py imports cv2 / matplotlib at module level for its visualisation helpers; the loss helpers never touch them
+  for name in ('cv2', 'matplotlib', 'matplotlib.cm', 'matplotlib.backends', 'matplotlib.backends.backend_agg', 'matplotlib.figure'):
+    if name not in sys.modules:
+      try:
+        importlib.import_module(name)
+      except Exception:
+        m = types.ModuleType(name)
+        m.cm = m.FigureCanvasAgg = m.Figure = object
+        sys.modules[name] = m
+  crit = importlib.import_module('ibrnet.criterion')
+  out = {}
+  for seed in cases.CRITERION_SEEDS:
+    for name, fn, leaves in cases.criterion_cases(crit, seed):
+      v = fn()
+      out[f'seed{seed}/{name}/value'] = npy(v)
+      for i, gr in enumerate(torch.autograd.grad(v, leaves)):
+        out[f'seed{seed}/{name}/grad{i}'] = npy(gr)
+  np.savez_compressed(os.path.join(HERE, 'criterion.npz'), **out)
+  print('criterion', len(out), 'arrays')
+
+
+def module_structure_goldens():
+  """What the adapter sees of the reference's own nn.Modules (tests/test_model_adapter.py): for DynibarStatic / DynibarDynamic / MotionMLP under
+  both argument sets, and for the feature network ResNet, the state dict (names in order, shapes, dtypes), which entries are parameters, and the
+  constructor-dependent attributes the adapter reads.  Names and shapes only: no values."""
+  import json
+  FN = ref.feature_network
+
+  def record(mod):
+    return {'state_dict': [[k, list(v.shape), str(v.dtype).replace('torch.', '')] for k, v in mod.state_dict().items()],
+            'parameters': [k for k, _ in mod.named_parameters()],
+            'attrs': {a: getattr(mod, a) for a in cases.MODULE_ATTRS if isinstance(getattr(mod, a, None), (bool, int, float))}}
+
+  out = {}
+  for cfg, kw in sorted(cases.MODULE_ARG_SETS.items()):
+    args = ref_args(**kw)
+    out[cfg + '/static'] = record(NET.DynibarStatic(args, in_feat_ch=32, n_samples=64))
+    out[cfg + '/dynamic'] = record(NET.DynibarDynamic(args, in_feat_ch=32, n_samples=64, shift=5.0))
+    out[cfg + '/motion'] = record(NET.MotionMLP(num_basis=cases.NUM_BASIS))
+  out['resnet/coarse_only=False'] = record(FN.ResNet(coarse_out_ch=32, fine_out_ch=32, coarse_only=False))
+  out['resnet/default'] = record(FN.ResNet(coarse_out_ch=32, fine_out_ch=32))
+  with open(os.path.join(HERE, 'reference_modules.json'), 'w') as f:
+    json.dump(out, f, indent=0, sort_keys=True)
+    f.write('\n')
+  print('reference_modules', {k: len(v['state_dict']) for k, v in out.items()})
+
+
 if __name__ == '__main__':
   import sys
+  if 'criterion' in sys.argv[1:]:
+    criterion_goldens()
+    sys.exit(0)
+  if 'modules' in sys.argv[1:]:
+    module_structure_goldens()
+    sys.exit(0)
   if 'camera_format' in sys.argv[1:]:
     camera_format_goldens()
     sys.exit(0)
@@ -570,3 +646,5 @@ if __name__ == '__main__':
   camera_format_goldens()
   cross_axis_goldens()
   image_goldens(63, 'image_nvi_tail3.npz')
+  criterion_goldens()
+  module_structure_goldens()

@@ -56,3 +56,33 @@ def load_numpy_state(module, sd):
   own = module.state_dict()
   module.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items() if k in own}, strict=True)
   return module.eval()
+
+
+def recorded(key, shift=None):
+  """A module with the recorded structure of one of the reference's own modules (tests/golden/reference_modules.json, written by
+  tests/golden/make_golden.py from the real classes): its state dict key for key, in order, with the recorded shapes and dtypes, the same
+  entries registered as parameters (the others as buffers) and the constructor-dependent attributes the adapter reads.  Values are zeros.
+  key: '<nvidia_eval|kid_running>/<static|dynamic|motion>' or 'resnet/<coarse_only=False|default>'; shift overrides DynibarDynamic's."""
+  import json
+  import os
+  with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_modules.json')) as f:
+    rec = json.load(f)[key]
+  params = set(rec['parameters'])
+  m = _Holder()
+  for name, shape, dtype in rec['state_dict']:
+    parts = name.split('.')
+    cur = m
+    for p in parts[:-1]:
+      if p not in cur._modules:
+        cur.add_module(p, _Holder())
+      cur = cur._modules[p]
+    t = torch.zeros(shape, dtype=getattr(torch, dtype))
+    if name in params:
+      cur.register_parameter(parts[-1], nn.Parameter(t, requires_grad=t.is_floating_point()))
+    else:
+      cur.register_buffer(parts[-1], t)
+  for a, v in rec['attrs'].items():
+    setattr(m, a, v)
+  if shift is not None and 'shift' in rec['attrs']:
+    m.shift = shift
+  return m

@@ -38,7 +38,7 @@ def test_frame_functions_and_abi_gather_on_one_rccl_rank():
 def test_bench_multi_rank_path_on_one_rccl_rank(gather):
   """bench.py --force-dist: the N > 1 control flow of the bench (nccl process group, all_gather_into_tensor per step, dist.barrier() fences, max over ranks,
   the frame leg tiled through render_single_image_nvi) with one rank."""
-  r = _run([os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--gather', gather, '--steps', '4', '--warmup', '1', '--cpu-rays', '0', '--no-traffic',
+  r = _run([os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--full', '--gather', gather, '--steps', '4', '--warmup', '1', '--cpu-rays', '0', '--no-traffic',
             '--frame-only'])
   assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
   lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

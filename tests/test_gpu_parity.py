@@ -159,7 +159,7 @@ def test_motion_mlp(dev, kw):
 
 
 def _golden(golden_dir, fn):
-  return dict(np.load(os.path.join(golden_dir, fn)))
+  return cases.load_golden(golden_dir, fn)
 
 
 def test_ray_sampler(dev, golden_dir):
@@ -305,7 +305,7 @@ def test_train_static_step(dev, kw):
 def test_static_bootstrap_step_drop_in(dev, golden_dir, kid):
   """train.py:116-199 through render_rays_mono on DataParallel-wrapped modules: loss.backward() fills the modules' .grad; against the
   real reference's autograd gradients (golden) and the oracle's"""
-  parity.check_static_bootstrap_step(dev, dict(np.load(os.path.join(golden_dir, 'train_static.npz'))), kid=kid)
+  parity.check_static_bootstrap_step(dev, _golden(golden_dir, 'train_static.npz'), kid=kid)
 
 
 @pytest.mark.parametrize('kw', [dict(name='small', S=64), dict(name='harsh', S=32, R=4), dict(name='kid', S=48, R=4), dict(name='many', S=16, R=3),

@@ -1,7 +1,9 @@
 """The drop-in must accept the reference's own model objects: nn.Modules, DataParallel-wrapped (model.py:134-159, :382-397), for BOTH
 argument sets the reference ships -- Nvidia eval (anti_alias_pooling=1, mask_rgb=0: configs_nvidia/eval_balloon1_long.txt:21-22) and
 the monocular configs (anti_alias_pooling=0, mask_rgb=1: configs/train_kid-running.txt:41-42, where DynibarStatic has NO `s`
-parameter, mlp_network.py:330-331).  Packing is host code, so all of this runs without a GPU."""
+parameter, mlp_network.py:330-331).  Packing is host code, so all of this runs without a GPU.  The reference's own modules enter as
+their recorded structure (tests/golden/reference_modules.json: state dict names, order, shapes, parameters and constructor attributes,
+written by tests/golden/make_golden.py from the real classes), so that nothing here needs the reference itself."""
 import types
 
 import numpy as np
@@ -9,11 +11,10 @@ import pytest
 import torch
 
 import cases
-import refimport
 import refmodules
 from dynibar_amd import ops, render_ray, synthetic as syn
 
-ARG_SETS = {'nvidia_eval': dict(anti_alias_pooling=1, mask_rgb=0), 'kid_running': dict(anti_alias_pooling=0, mask_rgb=1)}
+ARG_SETS = cases.MODULE_ARG_SETS
 
 
 def _args(name):
@@ -37,12 +38,10 @@ def _standin(kind, args, shift=0.0):
 
 
 def _real(kind, args, shift=0.0):
-  NET = refimport.import_reference().mlp_network
-  if kind == 'static':
-    return NET.DynibarStatic(args, in_feat_ch=32, n_samples=64)
-  if kind == 'dynamic':
-    return NET.DynibarDynamic(args, in_feat_ch=32, n_samples=64, shift=shift)
-  return NET.MotionMLP(num_basis=cases.NUM_BASIS)
+  """The reference's DynibarStatic / DynibarDynamic(shift) / MotionMLP(num_basis 6) as constructed with `args`, by their recorded structure."""
+  cfg = [k for k, v in ARG_SETS.items() if all(getattr(args, a) == b for a, b in v.items())]
+  assert len(cfg) == 1, 'no recorded reference module for these arguments'
+  return refmodules.recorded(f'{cfg[0]}/{kind}', shift=shift if kind == 'dynamic' else None)
 
 
 def _check_adapter(mods, cfg, wrap):
@@ -76,17 +75,15 @@ def test_adapter_accepts_modules(cfg, wrap):
   _check_adapter(_standin, cfg, wrap)
 
 
-@pytest.mark.skipif(not refimport.have_reference(), reason='needs /root/reference (build container only)')
 @pytest.mark.parametrize('cfg', sorted(ARG_SETS))
 @pytest.mark.parametrize('wrap', [False, True])
 def test_adapter_accepts_the_real_reference_modules(cfg, wrap):
   _check_adapter(_real, cfg, wrap)
 
 
-@pytest.mark.skipif(not refimport.have_reference(), reason='needs /root/reference (build container only)')
 @pytest.mark.parametrize('cfg', sorted(ARG_SETS))
 def test_standins_mirror_the_real_modules(cfg):
-  """tests/refmodules.py is what the GPU box feeds the adapter: its state dicts must be the reference's, key for key."""
+  """refmodules.like_reference is what the GPU tests feed the adapter: its state dicts must be the reference's, key for key."""
   args = _args(cfg)
   for kind in ('static', 'dynamic', 'motion'):
     real, mine = _real(kind, args).state_dict(), _standin(kind, args).state_dict()
@@ -129,13 +126,11 @@ def test_unsupported_module_variants_are_rejected_by_shape():
     ops.DynamicNet(D, 'cpu')
 
 
-@pytest.mark.skipif(not refimport.have_reference(), reason='needs /root/reference (build container only)')
 def test_encoder_packs_the_real_reference_module():
   """dynibar_amd.feature_network.ResNet.from_module takes the reference's ResNet (DataParallel-wrapped like model.py:142-151); the
   decoder layers its state dict also carries are ignored like its forward ignores them."""
   from dynibar_amd import feature_network
-  FN = refimport.import_reference().feature_network
-  net = FN.ResNet(coarse_out_ch=32, fine_out_ch=32, coarse_only=False)
+  net = refmodules.recorded('resnet/coarse_only=False')  # FN.ResNet(coarse_out_ch=32, fine_out_ch=32, coarse_only=False)
   sd = {k: torch.from_numpy(v) for k, v in syn.make_encoder_weights(2).items()}
   net.load_state_dict(sd, strict=False)
   enc = feature_network.ResNet.from_module(torch.nn.DataParallel(net))
@@ -188,15 +183,13 @@ def test_checkpoint_files_load_into_the_adapter(tmp_path):
     checkpoint.load_model({'net_fine_st': {}}, device='cpu')
 
 
-@pytest.mark.skipif(not refimport.have_reference(), reason='needs /root/reference (build container only)')
 def test_checkpoint_of_the_real_reference_modules(tmp_path):
   """The same through state dicts produced by the reference's own nn.Modules (what de_parallel(net).state_dict() saves)."""
   from dynibar_amd import checkpoint
   pc, pf, W = _checkpoint_files(tmp_path, modules=_real)
   m = checkpoint.load_model(pc, pf, device='cpu')
   assert torch.equal(render_ray._static_net(m, 'net_coarse_st', _args('nvidia_eval'), 'cpu').blob, ops.StaticNet(cases.model_weights(0)['net_coarse_st'], 'cpu', True, False).blob)
-  FN = refimport.import_reference().feature_network
-  net = FN.ResNet(coarse_out_ch=32, fine_out_ch=32)
+  net = refmodules.recorded('resnet/default')  # FN.ResNet(coarse_out_ch=32, fine_out_ch=32)
   torch.save({'net_coarse_st': m.net_coarse_st, 'feature_net': net.state_dict()}, str(tmp_path / 'x.pth'))  # incl. the decoder layers forward never runs
   m2 = checkpoint.load_model(str(tmp_path / 'x.pth'), device='cpu')
   assert m2.feature_net._encoder('cpu').blob.numel() == ops.Encoder(syn.make_encoder_weights(0), 'cpu').blob.numel()

@@ -15,7 +15,7 @@ TOL = dict(rtol=2e-6, atol=2e-6)
 
 
 def load(golden_dir, name):
-  return dict(np.load(os.path.join(golden_dir, name)))
+  return cases.load_golden(golden_dir, name)
 
 
 def close(a, b, **kw):

@@ -30,7 +30,7 @@ python $OLDPWD/tools/rocpd_summary.py traffic $OUT/${TAG}_traffic.json $DBS_B > 
 python $OLDPWD/tools/rocpd_summary.py traffic $OUT/${TAG}_frame_traffic.json $DBS_F > /dev/null 2>&1
 cd $OLDPWD
 python tools/framebench.py > $OUT/${TAG}_frame_nvi_288x512.txt 2>&1
-python bench.py > $OUT/${TAG}_bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/${TAG}_bench_n1.json 2> $OUT/bench_n1.err
 # keep only the summaries (the databases are large)
 find $OUT -name '*.db' -delete; find $OUT -type d -empty -delete
 ls -la $OUT

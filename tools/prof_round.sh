@@ -1,5 +1,5 @@
 export TMPDIR=/tmp; cd /tmp; R=/root/repo; O=$R/gpurun_out
-B="python $R/bench.py --steps 10 --warmup 2 --cpu-rays 0 --no-x6"
+B="python $R/bench.py --full --steps 10 --warmup 2 --cpu-rays 0 --no-x6"
 timeout 200 rocprofv3 --kernel-trace --stats -d $O/prof_r1i -o bench -- $B > $O/prof_r1i.log 2>&1; echo stats rc=$?
 timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_r1i_f -o bench -- $B > $O/pmc_r1i_f.log 2>&1; echo fetch rc=$?
 timeout 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_r1i_w -o bench -- $B > $O/pmc_r1i_w.log 2>&1; echo write rc=$?
