@@ -36,7 +36,8 @@ static const char* const g_prof_names[DYN_K_COUNT] = {
     "k_fine_samples", "k_static_ref_feat", "k_static_views", "k_static_points", "k_static_blend", "k_selftest", "k_dynamic_time_feat",
     "k_dynamic_views", "k_dynamic_points", "k_motion_mlp", "k_trajectory_points", "k_render_flows", "k_expected_scene_flow", "k_image_rays",
     "k_static_points_qkv", "k_dynamic_points_qkv", "k_enc_conv7", "k_enc_conv3", "k_enc_conv1", "k_enc_block_out",
-    "k_train_gemm", "k_train_rows", "k_train_attn", "k_gather_bwd", "k_motion_zero_tail", "k_ragged_plan"};
+    "k_train_gemm", "k_train_rows", "k_train_attn", "k_gather_bwd", "k_motion_zero_tail", "k_ragged_plan",
+    "k_splat_project", "k_splat_keys", "k_splat_sort", "k_splat_resolve", "k_sobel_alpha", "k_vv_finish"};
 
 static void prof_flush(int slot) {
   for (int i = 0; i < g_prof.used[slot]; ++i) {
@@ -1904,3 +1905,6 @@ extern "C" int dyn_plucker_src(const float* pts, int per_view_pts, const float* 
              per_view_pts ? n_pts * 3 : 0L, cams, R, S, V, out);
   return 0;
 }
+
+// forward splatting of the virtual source views (render_source_vv.py) -- its own header, this unit's flags
+#include "dyn_splat.h"

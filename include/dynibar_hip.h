@@ -521,6 +521,59 @@ int dyn_comm_destroy(void* comm);
  * tiles are padded to the common size by the caller: balanced tiles differ by at most one ray). */
 int dyn_gather_tiles(const float* send, float* recv, long rows_per_rank, int cols, void* comm, void* stream);
 
+/* ====== virtual source views of the monocular path (render_source_vv.py, the producer of source_virtual_views_WxH/NNNNN/KK.png and
+ * source_vv_poses.npy that ibrnet/data_loaders/monocular.py:312-325, 374-387 load) =====================================================
+ * The splat of the third-party `splatting` package (render_source_vv.py:12, 58): source pixel (x, y) of batch entry b lands at
+ * (X, Y) = (x + flow[b,0,y,x], y + flow[b,1,y,x]) and adds w * value to its four bilinear corners nw, ne, sw, se (corner 0..3; weights
+ * (x0+1-X)(y0+1-Y), (X-x0)(y0+1-Y), (x0+1-X)(Y-y0), (X-x0)(Y-y0) with x0 = floor(X), y0 = floor(Y)); corners off the image, and
+ * non-finite targets, contribute nothing.  Every output pixel is summed SEQUENTIALLY in ascending contribution id 4 (y W + x) + corner,
+ * starting at +0.0, so the result is bitwise reproducible (no float atomics: a stable radix sort builds the inverted index).
+ * Workspace: DEVICE scratch of dyn_splat_workspace_bytes(B,H,W) bytes (0: unsupported shape, B*H*W > 2^28), shared by both entries. */
+size_t dyn_splat_workspace_bytes(int B, int H, int W);
+typedef struct {
+  int B, C, H, W;
+  const float* frame;        /* [B,C,H,W] */
+  const float* flow;         /* [B,2,H,W] */
+  const float* multiplier;   /* [B,H,W] or NULL: contributions are w * (frame * multiplier) (the package's linear / softmax forms) */
+  int normalize;             /* 0: summation.  1: out = num / (den + eps), den = the splatted multiplier (1 where multiplier is NULL) */
+  float eps;                 /* the package's eps (1e-7) */
+  float* out;                /* [B,C,H,W] */
+  void* workspace;
+  size_t workspace_bytes;
+} DynSplatParams;
+int dyn_splat(const DynSplatParams* p, void* stream);
+
+/* render_forward_splat (render_source_vv.py:15-66) fused: P = depth K_src^-1 [x y 1], Q = K_dst (R P + t), flow = Q.xy / max(Q.z, 1e-8)
+ * - (x, y), importance = 1 / Q.z, w = (importance - min_b) / (max_b - min_b + 1e-6) * 20 - 10 (per batch entry), then the softmax splat of
+ * [src | importance | 1] with multiplier exp(w).  The probes (NULL to skip) receive the intermediate values the kernels actually used. */
+typedef struct {
+  int B, H, W, C;
+  const float* src;          /* [B,H,W,C] channels-last, as the reference passes it */
+  const float* depth;        /* [B,H,W] */
+  const float* k_src_inv;    /* [B,3,3] */
+  const float* rot;          /* [B,3,3] */
+  const float* k_dst;        /* [B,3,3] */
+  const float* t;            /* [B,3] */
+  float eps;                 /* the package's eps (1e-7) */
+  float* feat;               /* [B,C,H,W] warp_feature */
+  float* disp;               /* [B,1,H,W] warp_disp */
+  float* mask;               /* [B,1,H,W] or NULL: the splatted ones channel (the reference's commented-out warp_mask, :64) */
+  float* flow;               /* probe [B,2,H,W] or NULL */
+  float* importance;         /* probe [B,H,W] or NULL */
+  float* weight_exp;         /* probe [B,H,W] or NULL: exp(w) */
+  void* workspace;
+  size_t workspace_bytes;
+} DynForwardSplatParams;
+int dyn_forward_splat(const DynForwardSplatParams* p, void* stream);
+
+/* sobel_fg_alpha (render_source_vv.py:118-128): x [B,1,H,W] -> alpha [B,1,H,W] = exp(-beta |sobel(x)|), kornia spatial_gradient
+ * (mode='sobel', normalized=False) with replicate padding */
+int dyn_sobel_alpha(const float* x, int B, int H, int W, float beta, float* alpha, void* stream);
+
+/* the per-view epilogue of render_source_vv.py:313-330: feat [B,C,H,W] (C >= 4: rgb in 0..255, alpha) -> out [B,H,W,3] uint8 =
+ * uint8(255 clip(clip(rgb / 255, 0, 1) m, 0, 1)), m = erosion(clip(alpha, 0, 1) > 0.5, disk(1)); out-of-image neighbours do not erode */
+int dyn_vv_finish(const float* feat, int B, int C, int H, int W, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
