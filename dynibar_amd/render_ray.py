@@ -302,7 +302,8 @@ def _dual_branch(model, names, args, projector, ray_batch, featmaps_dy, featmaps
     raw_st = train_static.static_raw(net_st, flags, views_st, rgb_feat_st, ray_o, ray_d, pts, ray_diff_st, mask_st)
   else:
     raw_st = _static_net(model, names['st'], args, dev)(views_st, ray_o, ray_d, pts, rgb_feat_st, ray_diff_st, mask_st)
-  return dict(raw_dy=raw_dy, raw_st=raw_st, pm_dy=pm_dy, pm_st=pm_st, coeff=coeff, pts_seq=pts_seq, views_dy=views_dy, basis=basis, traj=traj, pts=pts, n_views=len(rows))
+  return dict(raw_dy=raw_dy, raw_st=raw_st, pm_dy=pm_dy, pm_st=pm_st, coeff=coeff, pts_seq=pts_seq, views_dy=views_dy, basis=basis, traj=traj, pts=pts, n_views=len(rows),
+              rows=rows)
 
 
 def _finish(stage, z_vals, keys2, keys1):
@@ -331,7 +332,12 @@ def _motion_outputs(out, stage, ray_batch, ref_frame_idx, sf_off, flow_views=Non
   views = stage['views_dy']
   fv = stage['n_views'] if flow_views is None else min(flow_views, stage['n_views'])
   uv = ray_batch['uv_grid'].float().contiguous()
-  if stage['pts_seq'] is None:  # the fused eval form: the flows form the displaced points themselves (the first fv views: a prefix of the rows)
+  if stage['pts_seq'] is None and _needs_graph(out['weights']):
+    # fused stage (the motion path carries no graph) whose weights do, because a net or the static maps train: the flows' gradient reaches them
+    # through the weights (render_ray.py:333-358 does not detach them).  The first fv displaced points are materialised without a graph.
+    coeff, basis, _, ref = stage['traj']
+    flows = train_motion.render_flows(out['weights'], _traj(coeff, basis, stage['pts'], stage['rows'][:fv], ref), views.proj, uv)
+  elif stage['pts_seq'] is None:  # the fused eval form: the flows form the displaced points themselves (the first fv views: a prefix of the rows)
     coeff, basis, rows_dev, ref = stage['traj']
     flows = torch.empty((fv, R, 2), dtype=torch.float32, device=out['weights'].device)
     k = ops._Keep()

@@ -409,11 +409,14 @@ def train_static_goldens():
   print('train_static', len(out), 'arrays', sum(v.nbytes for v in out.values()) // 1024, 'KiB')
 
 
-def mono_train_grad_goldens(name='few', S=16, R=4):
+def mono_train_grad_goldens(name='few', S=16, R=4, weights='trained', fname='mono_train_grad.npz'):
   """The reference's main training iteration (train.py:203-467) on the REAL modules with the REAL autograd: render_rays_mono(is_train=True)
   under grad mode, the script's loss (tests/cases.mono_train_loss: the full sum, and the flow / cycle / regularisation / colour terms on
   their own so that every gradient route is visible), loss.backward().  Stores a digest (cases.grad_digest) of the gradient of every
-  parameter of net_coarse_st, net_coarse_dy, motion_mlp, of the trajectory basis and of the three feature-map sets."""
+  parameter of net_coarse_st, net_coarse_dy, motion_mlp, of the trajectory basis and of the three feature-map sets.
+  weights='trained' (mono_train_grad.npz): trained-scale weights, whose saturated densities silence the flow term's route through the compositing
+  weights; weights='init' (mono_train_grad_init.npz): the initialisation-scale weights of cases.model_weights(0), where that route is live."""
+  W = cases.model_weights_trained() if weights == 'trained' else cases.model_weights(0)
   out = {}
   scene, o, d, uv, pix = cases.scene_case(name)
   o, d, uv = o[:R], d[:R], uv[:R]
@@ -421,7 +424,7 @@ def mono_train_grad_goldens(name='few', S=16, R=4):
   tgt = cases.train_batch_targets(R)
   args = ref_args(anti_alias_pooling=0, mask_rgb=1)
   for lname, terms in cases.MONO_TRAIN_LOSSES.items():
-    model = build_ref_model(cases.model_weights_trained(), S, 2 * S, args, shift=5.0)
+    model = build_ref_model(W, S, 2 * S, args, shift=5.0)
     for m in (model.net_coarse_st, model.net_coarse_dy, model.motion_mlp):
       m.train()
     model.trajectory_basis = model.trajectory_basis.clone().requires_grad_(True)
@@ -442,8 +445,8 @@ def mono_train_grad_goldens(name='few', S=16, R=4):
         continue
       for dk, dv in cases.grad_digest(g).items():
         out[f'{lname}/{k}/{dk}'] = npy(dv)
-  np.savez_compressed(os.path.join(HERE, 'mono_train_grad.npz'), **out)
-  print('mono_train_grad', len(out), 'arrays', sum(v.nbytes for v in out.values()) // 1024, 'KiB')
+  np.savez_compressed(os.path.join(HERE, fname), **out)
+  print(fname, len(out), 'arrays', sum(v.nbytes for v in out.values()) // 1024, 'KiB')
 
 
 def cross_axis_goldens():
@@ -611,6 +614,9 @@ if __name__ == '__main__':
     sys.exit(0)
   if 'mono_train_grad' in sys.argv[1:]:
     mono_train_grad_goldens()
+    sys.exit(0)
+  if 'mono_train_grad_init' in sys.argv[1:]:
+    mono_train_grad_goldens(weights='init', fname='mono_train_grad_init.npz')
     sys.exit(0)
   if 'train_static' in sys.argv[1:]:
     train_static_goldens()

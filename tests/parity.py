@@ -2296,21 +2296,43 @@ def _digest_close(got, ref_d, what, n, gmax):
   assert_close(d['head'], torch.from_numpy(ref_d['head']), 3e-4 * am + 3e-6 * gmax + 1e-12, 2e-3, f'{what} first values')
 
 
-def oracle_mono_train_step(terms, dtype=torch.float32, case=None, device='cpu'):
+# the leaves of one training iteration, grouped as a fine-tune freezes them: the three nets, the trajectory basis, the three feature-map sets
+TRAIN_LEAVES = ('st', 'dy', 'motion_mlp', 'basis', 'featmaps_ref', 'featmaps_anchor', 'featmaps_static')
+_LEAF_NETS = {'st': 'net_coarse_st', 'dy': 'net_coarse_dy', 'motion_mlp': 'motion_mlp'}
+_FEATMAP_KEYS = {'featmaps_ref': 'featmaps', 'featmaps_anchor': 'featmaps_anchor', 'featmaps_static': 'static_featmaps'}
+
+
+def leaf_of(grad_key):
+  """gradient key ('net_coarse_dy.rgb_fc.weight', 'basis', 'featmaps_static', ...) -> its TRAIN_LEAVES group"""
+  head = grad_key.split('.')[0]
+  return {v: k for k, v in _LEAF_NETS.items()}.get(head, head)
+
+
+def _trainable(trainable):
+  t = set(TRAIN_LEAVES) if trainable is None else set(trainable)
+  assert t <= set(TRAIN_LEAVES), f'unknown leaves {sorted(t - set(TRAIN_LEAVES))}'
+  return t
+
+
+def oracle_mono_train_step(terms, dtype=torch.float32, case=None, device='cpu', weights='trained', trainable=None):
   """torch autograd through the oracle's render_rays_mono_train + the restated train.py loss -> (loss, {name: grad}).  dtype float64: the same
-  graph in double (the arbiter of how well-conditioned each gradient is); device: where the eager graph runs (the large case runs on the GPU)."""
+  graph in double (the arbiter of how well-conditioned each gradient is); device: where the eager graph runs (the large case runs on the GPU);
+  weights: 'trained' (cases.model_weights_trained) or 'init' (cases.model_weights(0)); trainable: the TRAIN_LEAVES groups that require grad
+  (None: all), the others are frozen and their gradients None."""
   c = case or MONO_TRAIN_CASE
+  t = _trainable(trainable)
   scene, o, d, uv, _ = cases.scene_case(c['name'])
   o, d, uv = o[:c['R']], d[:c['R']], uv[:c['R']]
   sc, fidx, temb, toff = cases.anchor_case(scene, num_vv=c['num_vv'])
   cv = lambda v: (v.to(dtype) if v.is_floating_point() else v).to(device) if isinstance(v, torch.Tensor) else v
-  W = {k: {n: cv(v.clone()).requires_grad_(True) for n, v in O.tdict(sd).items()} for k, sd in cases.model_weights_trained().items()}
+  on = {net: leaf in t for leaf, net in _LEAF_NETS.items()}
+  W = {k: {n: cv(v.clone()).requires_grad_(on.get(k, True)) for n, v in O.tdict(sd).items()} for k, sd in _weights(weights).items()}
   W['net_coarse_st'].pop('s', None)
-  basis = cv(O.init_dct_basis(cases.NUM_BASIS, cases.NUM_FRAMES).clone()).requires_grad_(True)
+  basis = cv(O.init_dct_basis(cases.NUM_BASIS, cases.NUM_FRAMES).clone()).requires_grad_('basis' in t)
   W['trajectory_basis'] = basis
   sc = {k: cv(v) for k, v in sc.items()}
-  fms = {k: sc[k].clone().requires_grad_(True) for k in ('featmaps', 'featmaps_anchor', 'static_featmaps')}
-  sc.update(fms)
+  fms = {leaf: sc[k].clone().requires_grad_(leaf in t) for leaf, k in _FEATMAP_KEYS.items()}
+  sc.update({k: fms[leaf] for leaf, k in _FEATMAP_KEYS.items()})
   tgt = {k: cv(v) for k, v in cases.train_batch_targets(c['R']).items()}  # drawn in fp32 whatever the graph's dtype: the same targets for every run
   prev = torch.get_default_dtype()
   torch.set_default_dtype(dtype)
@@ -2318,50 +2340,69 @@ def oracle_mono_train_step(terms, dtype=torch.float32, case=None, device='cpu'):
     ret = O.render_rays_mono_train(W, sc, cv(o), cv(d), cv(uv), fidx, tuple(cv(t) for t in temb), toff, c['S'], True, True, anti_alias_pooling=False, mask_rgb=True,
                                    num_vv=c['num_vv'], dy_shift=5.0)
     loss = cases.mono_train_loss(ret, tgt, terms)
-    loss.backward()
+    if loss.requires_grad:
+      loss.backward()
   finally:
     torch.set_default_dtype(prev)
-  grads = {'basis': basis.grad, 'featmaps_ref': fms['featmaps'].grad, 'featmaps_anchor': fms['featmaps_anchor'].grad,
-           'featmaps_static': fms['static_featmaps'].grad}
+  grads = {'basis': basis.grad}
+  grads.update({leaf: fm.grad for leaf, fm in fms.items()})
   for net in ('net_coarse_st', 'net_coarse_dy', 'motion_mlp'):
     for k, v in W[net].items():
       grads[f'{net}.{k}'] = v.grad
   return loss.detach(), grads
 
 
-def run_mono_train_step(device, terms, case=None):
-  """the HIP path: render_ray.render_rays_mono(is_train=True) on DataParallel-wrapped modules under grad mode, the restated loss, backward"""
+def mono_train_forward(device, case=None, weights='trained', trainable=None):
+  """render_ray.render_rays_mono(is_train=True) on DataParallel-wrapped modules under the caller's grad mode; the groups of TRAIN_LEAVES not in
+  `trainable` (None: all) are frozen the way a fine-tune freezes them: requires_grad_(False) on the module's parameters / the basis, feature maps
+  handed in without grad -> (ret, model, feature maps by leaf name)"""
   import types
   from dynibar_amd import projection, render_ray
   c = case or MONO_TRAIN_CASE
+  t = _trainable(trainable)
   scene, o, d, uv, _ = cases.scene_case(c['name'])
   o, d, uv = o[:c['R']], d[:c['R']], uv[:c['R']]
   sc, fidx, temb, toff = cases.anchor_case(scene, num_vv=c['num_vv'])
   args = types.SimpleNamespace(anti_alias_pooling=0, mask_rgb=1, input_dir=True, input_xyz=False, occ_weights_mode=0)
-  model = make_module_model(device, args, shift=5.0, weights=cases.model_weights_trained())
+  model = make_module_model(device, args, shift=5.0, weights=_weights(weights))
+  for leaf, net in _LEAF_NETS.items():
+    if leaf not in t:
+      getattr(model, net).requires_grad_(False)
+  if 'basis' not in t:
+    model.trajectory_basis.requires_grad_(False)
   batch = make_ray_batch(sc, o, d, uv, device)
   batch['anchor_src_rgbs'], batch['anchor_src_cameras'] = sc['anchor_src_rgbs'].to(device), sc['anchor_src_cameras'].to(device)
-  fms = [sc[k].to(device).requires_grad_(True) for k in ('featmaps', 'featmaps_anchor', 'static_featmaps')]
-  ret = render_ray.render_rays_mono(fidx, tuple(t.to(device) for t in temb), toff, batch, model, tuple(fms), projection.Projector(device), c['S'], args,
-                                    inv_uniform=True, det=True, is_train=True, num_vv=c['num_vv'])
+  fms = {leaf: sc[k].to(device).requires_grad_(leaf in t) for leaf, k in _FEATMAP_KEYS.items()}
+  ret = render_ray.render_rays_mono(fidx, tuple(t.to(device) for t in temb), toff, batch, model, tuple(fms[k] for k in _FEATMAP_KEYS), projection.Projector(device),
+                                    c['S'], args, inv_uniform=True, det=True, is_train=True, num_vv=c['num_vv'])
+  return ret, model, fms
+
+
+def run_mono_train_step(device, terms, case=None, weights='trained', trainable=None):
+  """the HIP path: render_ray.render_rays_mono(is_train=True) on DataParallel-wrapped modules under grad mode, the restated loss, backward
+  (trainable: as mono_train_forward; frozen leaves keep .grad None)"""
+  from dynibar_amd import render_ray
+  c = case or MONO_TRAIN_CASE
+  ret, model, fms = mono_train_forward(device, c, weights, trainable)
   loss = cases.mono_train_loss(ret, cases.train_batch_targets(c['R']), terms)
   loss.backward()
-  grads = {'basis': model.trajectory_basis.grad, 'featmaps_ref': fms[0].grad, 'featmaps_anchor': fms[1].grad, 'featmaps_static': fms[2].grad}
+  grads = {'basis': model.trajectory_basis.grad}
+  grads.update({leaf: fm.grad for leaf, fm in fms.items()})
   for net in ('net_coarse_st', 'net_coarse_dy', 'motion_mlp'):
     for k, p in render_ray._unwrap(getattr(model, net)).named_parameters():
       grads[f'{net}.{k}'] = p.grad
   return loss.detach(), grads
 
 
-def check_train_mono(device, golden, losses=('full', 'flow', 'cycle', 'reg', 'rgb')):
+def check_train_mono(device, golden, losses=('full', 'flow', 'cycle', 'reg', 'rgb'), weights='trained'):
   """One iteration of the reference's main loop (train.py:203-467) through dynibar_amd.render_ray.render_rays_mono: the loss value and the
   gradient of EVERY parameter (DynibarStatic, DynibarDynamic, MotionMLP, trajectory basis) and of the three feature-map sets against the
   REAL reference's autograd (digests in tests/golden/mono_train_grad.npz), for the full loss and for single terms (so that the flow,
   cycle and regularisation routes into MotionMLP / the basis are each visible on their own)."""
   n_checked = 0
   for lname in losses:
-    loss, grads = run_mono_train_step(device, cases.MONO_TRAIN_LOSSES[lname])
-    assert_close(loss, torch.from_numpy(golden[f'{lname}/loss']), 1e-5, 2e-4, f'mono train [{lname}] loss')
+    loss, grads = run_mono_train_step(device, cases.MONO_TRAIN_LOSSES[lname], weights=weights)
+    assert_close(loss, torch.from_numpy(golden[f'{lname}/loss']), 1e-5, 2e-4, f'mono train [{lname}] loss' + ('' if weights == 'trained' else f' ({weights} weights)'))
     keys = sorted({k.split('/')[1] for k in golden if k.startswith(lname + '/') and k.count('/') == 2})
     gmax = max(float(golden[f'{lname}/{k}/absmax'][0]) for k in keys if not k.startswith('featmaps'))
     for k in keys:
@@ -2370,7 +2411,7 @@ def check_train_mono(device, golden, losses=('full', 'flow', 'cycle', 'reg', 'rg
       if g is None:
         assert float(ref_d['absmax'][0]) == 0.0, f'mono train [{lname}]: no gradient for {k} but the reference has one (max {float(ref_d["absmax"][0]):.2e})'
         continue
-      _digest_close(g, ref_d, f'mono train [{lname}] grad {k}', g.numel(), gmax)
+      _digest_close(g, ref_d, f'mono train [{lname}]' + ('' if weights == 'trained' else f' ({weights} weights)') + f' grad {k}', g.numel(), gmax)
       n_checked += 1
     missing = [k for k, g in grads.items() if g is not None and f'{lname}/{k}/proj' not in golden and float(g.abs().max()) > 0]
     assert not missing, f'mono train [{lname}]: gradients the reference does not produce: {missing[:5]}'
@@ -2380,7 +2421,7 @@ def check_train_mono(device, golden, losses=('full', 'flow', 'cycle', 'reg', 'rg
 MONO_TRAIN_LARGE = dict(name='train_large', S=64, R=256, num_vv=3)
 
 
-def check_train_mono_large(device, case=None):
+def check_train_mono_large(device, case=None, weights='trained'):
   """Section 8f-3 at the shape training runs at (configs/train_kid-running.txt: 64 samples, 7 + 3 dynamic views at the reference and at the anchor frame,
   15 static views) with hundreds of rays: the full train.py loss (cases.mono_train_loss, every term) and EVERY gradient -- all parameters of the three nets,
   the trajectory basis, the three feature-map sets -- as FULL tensors against autograd through the oracle run ON THE DEVICE (PyTorch eager fp32), with
@@ -2389,12 +2430,13 @@ def check_train_mono_large(device, case=None):
   fp32 atomic sums over hundreds of workgroups, so two identical steps differ in the last bits: the spread of two runs is measured and reported too."""
   c = case or MONO_TRAIN_LARGE
   terms = cases.MONO_TRAIN_LOSSES['full']
-  loss_a, g_a = run_mono_train_step(device, terms, case=c)
-  loss_b, g_b = run_mono_train_step(device, terms, case=c)
-  loss32, g32 = oracle_mono_train_step(terms, torch.float32, case=c, device=device)
-  loss64, g64 = oracle_mono_train_step(terms, torch.float64, case=c, device=device)
-  assert_close(loss_a, cpu(loss32), 1e-5, 2e-4, f'train large ({c["R"]} rays) loss vs oracle fp32 on the device')
-  assert_close(loss_a, cpu(loss64).float(), 1e-5, 2e-4, f'train large ({c["R"]} rays) loss vs oracle fp64')
+  loss_a, g_a = run_mono_train_step(device, terms, case=c, weights=weights)
+  loss_b, g_b = run_mono_train_step(device, terms, case=c, weights=weights)
+  loss32, g32 = oracle_mono_train_step(terms, torch.float32, case=c, device=device, weights=weights)
+  loss64, g64 = oracle_mono_train_step(terms, torch.float64, case=c, device=device, weights=weights)
+  tag = 'train large' + ('' if weights == 'trained' else f' ({weights} weights)')
+  assert_close(loss_a, cpu(loss32), 1e-5, 2e-4, f'{tag} ({c["R"]} rays) loss vs oracle fp32 on the device')
+  assert_close(loss_a, cpu(loss64).float(), 1e-5, 2e-4, f'{tag} ({c["R"]} rays) loss vs oracle fp64')
   keys = [k for k, v in g64.items() if v is not None]
   gmax = max(float(g64[k].abs().max()) for k in keys if not k.startswith('featmaps'))
   worst, spread, n = 0.0, 0.0, 0
@@ -2404,19 +2446,305 @@ def check_train_mono_large(device, case=None):
     got, got_b = g_a.get(k), g_b.get(k)
     scale = float(ref64.abs().max())
     if got is None:
-      assert scale == 0.0, f'train large: no gradient for {k} but the oracle has one (max {scale:.2e})'
+      assert scale == 0.0, f'{tag}: no gradient for {k} but the oracle has one (max {scale:.2e})'
       continue
     got, got_b = cpu(got).double().reshape(ref64.shape), cpu(got_b).double().reshape(ref64.shape)
     cond = 3.0 * (ref32 - ref64).abs()
-    assert_close(got, ref64, 2e-4 * scale + 2e-6 * gmax, 1e-3, f'train large grad {k} vs oracle fp64 (max |g| {scale:.2e}, {ref64.numel()} values)', extra=cond)
-    assert_close(got, ref32, 2e-4 * scale + 2e-6 * gmax, 1e-3, f'train large grad {k} vs oracle fp32 on the device (max |g| {scale:.2e})', extra=cond)
+    assert_close(got, ref64, 2e-4 * scale + 2e-6 * gmax, 1e-3, f'{tag} grad {k} vs oracle fp64 (max |g| {scale:.2e}, {ref64.numel()} values)', extra=cond)
+    assert_close(got, ref32, 2e-4 * scale + 2e-6 * gmax, 1e-3, f'{tag} grad {k} vs oracle fp32 on the device (max |g| {scale:.2e})', extra=cond)
     if scale > 1e-3 * gmax:
       worst = max(worst, float((got - ref64).abs().max()) / scale)
       sp = float((got - got_b).abs().max()) / scale
-      record_margin(f'train large run-to-run spread of {k} (two identical steps; fp32 atomics), fraction of 2e-4 max|g|', sp, 2e-4)
+      record_margin(f'{tag} run-to-run spread of {k} (two identical steps; fp32 atomics), fraction of 2e-4 max|g|', sp, 2e-4)
       spread = max(spread, sp)
     n += 1
   assert n >= 90, 'every parameter of the three nets, the basis and the feature maps'
   assert spread < 2e-4, f'two identical training steps differ by {spread:.1e} of the largest gradient'
-  print(f'  train large: {n} gradient tensors at {c["R"]} rays x {c["S"]} samples; worst error {worst:.1e} of a tensor\'s largest gradient, run-to-run spread {spread:.1e}')
+  print(f'  {tag}: {n} gradient tensors at {c["R"]} rays x {c["S"]} samples; worst error {worst:.1e} of a tensor\'s largest gradient, run-to-run spread {spread:.1e}')
   return worst, spread
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# training a subset of the model: which kernels run depends on which inputs carry a graph (render_ray._needs_graph / wants_grad)
+# ----------------------------------------------------------------------------------------------------------------------
+FREEZE_PATTERNS = {
+    'all': TRAIN_LEAVES,
+    'st_dy': ('st', 'dy'),
+    'dy': ('dy',),
+    'st': ('st',),
+    'featmaps_static': ('featmaps_static',),
+    'motion_mlp': ('motion_mlp',),
+    'basis': ('basis',),
+    'motion_mlp_basis': ('motion_mlp', 'basis'),
+    'featmaps': ('featmaps_ref', 'featmaps_anchor', 'featmaps_static'),
+}
+
+
+def check_train_mono_frozen(device, trainable, terms='full', golden=None, weights='init'):
+  """One training iteration (MONO_TRAIN_CASE) with only the TRAIN_LEAVES groups in `trainable` requiring grad, for the loss `terms`
+  (a cases.MONO_TRAIN_LOSSES name): the loss against the oracle run with the same leaves frozen and against the real reference; every trainable
+  leaf's full gradient against that oracle in fp64 and fp32 (the limits of check_train_mono_large) and its digest against the real reference's
+  all-trainable run (tests/golden/mono_train_grad_init.npz: a leaf's gradient does not depend on which other leaves are frozen); every frozen
+  leaf's .grad None."""
+  if golden is None:
+    golden = cases.load_golden(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'), f'mono_train_grad{"" if weights == "trained" else "_" + weights}.npz')
+  t = _trainable(trainable)
+  tag = f'mono train frozen [{terms}] trainable={{{",".join(sorted(t))}}}'
+  loss, got = run_mono_train_step(device, cases.MONO_TRAIN_LOSSES[terms], weights=weights, trainable=t)
+  loss32, g32 = oracle_mono_train_step(cases.MONO_TRAIN_LOSSES[terms], torch.float32, weights=weights, trainable=t)
+  loss64, g64 = oracle_mono_train_step(cases.MONO_TRAIN_LOSSES[terms], torch.float64, weights=weights, trainable=t)
+  assert_close(loss, loss32, 1e-5, 2e-4, f'{tag} loss vs oracle fp32')
+  assert_close(loss, loss64.float(), 1e-5, 2e-4, f'{tag} loss vs oracle fp64')
+  assert_close(loss, torch.from_numpy(golden[f'{terms}/loss']), 1e-5, 2e-4, f'{tag} loss vs the reference')
+  keys = sorted({k.split('/')[1] for k in golden if k.startswith(terms + '/') and k.count('/') == 2})
+  gmax = max(float(golden[f'{terms}/{k}/absmax'][0]) for k in keys if not k.startswith('featmaps'))  # the all-trainable run's: the same whatever is frozen
+  n = 0
+  for k, ref64 in g64.items():
+    if leaf_of(k) not in t:
+      assert ref64 is None, f'{tag}: the oracle differentiated the frozen {k}'
+      assert got[k] is None, f'{tag}: frozen leaf {k} received a gradient'
+      continue
+    ref32 = g32[k]
+    if got[k] is None or ref64 is None:  # a trainable leaf this loss term does not reach
+      assert ref64 is None or float(ref64.abs().max()) == 0.0, f'{tag}: no gradient for {k} but the oracle has one (max {float(ref64.abs().max()):.2e})'
+      assert got[k] is None or float(got[k].abs().max()) == 0.0, f'{tag}: gradient for {k} where the oracle has none'
+      continue
+    g, ref64, ref32 = cpu(got[k]).double().reshape(ref64.shape), ref64.double(), ref32.double()
+    scale = float(ref64.abs().max())
+    cond = 3.0 * (ref32 - ref64).abs()
+    assert_close(g, ref64, 2e-4 * scale + 2e-6 * gmax, 1e-3, f'{tag} grad {k} vs oracle fp64 (max |g| {scale:.2e})', extra=cond)
+    assert_close(g, ref32, 2e-4 * scale + 2e-6 * gmax, 1e-3, f'{tag} grad {k} vs oracle fp32 (max |g| {scale:.2e})', extra=cond)
+    if f'{terms}/{k}/proj' in golden:
+      _digest_close(g, {dk: golden[f'{terms}/{k}/{dk}'] for dk in ('proj', 'absmax', 'head', 'l1')}, f'{tag} grad {k} vs the reference', g.numel(), gmax)
+    else:
+      assert scale == 0.0, f'{tag}: gradient for {k} that the reference does not produce'
+    n += 1
+  assert n > 0, f'{tag}: no trainable leaf was checked'
+  return n
+
+
+def check_train_mono_nothing_trainable(device, weights='init'):
+  """Grad mode with every leaf frozen must select exactly the inference kernels: every output bitwise equal to the torch.no_grad() run, and
+  a loss without grad_fn."""
+  c = MONO_TRAIN_CASE
+  with torch.no_grad():
+    ret0 = mono_train_forward(device, c, weights)[0]
+  ret1 = mono_train_forward(device, c, weights, trainable=())[0]
+  n = 0
+  for grp, d0 in ret0.items():
+    if d0 is None:
+      assert ret1[grp] is None, grp
+      continue
+    assert set(d0) == set(ret1[grp]), f'{grp}: output keys differ'
+    for k, v0 in d0.items():
+      v1 = ret1[grp][k]
+      if isinstance(v0, torch.Tensor):
+        assert not v1.requires_grad, f'{grp}/{k} carries a graph with nothing trainable'
+        assert_bitexact(v1, v0, f'nothing trainable under grad mode vs torch.no_grad(): {grp}/{k}')
+        n += 1
+  loss = cases.mono_train_loss(ret1, cases.train_batch_targets(c['R']), cases.MONO_TRAIN_LOSSES['full'])
+  assert loss.grad_fn is None and not loss.requires_grad, 'the loss has a graph with nothing trainable'
+  return n
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the motion path's autograd Functions one by one (dynibar_amd/train_motion.py) against fp64 autograd through the oracle's restatement
+# ----------------------------------------------------------------------------------------------------------------------
+def _fn_grad_close(got, g32, g64, what, atol_frac, rtol, extra=None):
+  """a Function's gradient vs the oracle's fp64 autograd: atol_frac of the tensor's largest gradient + rtol relative + the measured conditioning
+  allowance 3 x |oracle fp32 - oracle fp64| per element (as check_train_dual) [+ extra]"""
+  assert got is not None, f'{what}: no gradient'
+  g64 = g64.double()
+  scale = float(g64.abs().max())
+  assert scale > 0.0, f'{what}: the case has no gradient to compare'
+  cond = 3.0 * (g32.double() - g64).abs()
+  if extra is not None:
+    cond = cond + extra
+  assert_close(cpu(got).reshape(g64.shape), g64, atol_frac * scale + 1e-30, rtol, f'{what} (max |g| {scale:.2e})', extra=cond)
+  return float((cpu(got).double().reshape(g64.shape) - g64).abs().max()) / scale
+
+
+def check_gather_fn(device, name='few', S=16, R=None, F=None, maps=True, seed=0):
+  """train_motion.GatherFunction: d rgb_feat -> d feature maps (k_gather_bwd32_ray for F = 32 and S >= 8, k_gather_bwd32 below, k_gather_bwd for
+  other widths) and d displaced points (k_gather_bwd_pts32 / k_gather_bwd_pts) vs fp64 autograd through O.compute_with_motions.  maps=False:
+  the maps take no gradient (needs_input_grad[0] false), only the points do.  The points are the scene's samples displaced by a seeded
+  jitter, so that some leave the image or fall behind a camera ('harsh'); taps within 2e-3 px of an image edge (boundary_margin) get no
+  cotangent."""
+  from dynibar_amd import train_motion as TM
+  scene, o, d, uv, _ = cases.scene_case(name)
+  if R is not None:
+    o, d = o[:R], d[:R]
+  fm = scene['featmaps'] if F is None else scene['featmaps'][:, :F].contiguous()
+  Fw = fm.shape[1]
+  pts, _, _ = O.sample_along_camera_ray(o, d, scene['depth_range'], S, True, True)
+  Rn, V = pts.shape[0], scene['src_rgbs'].shape[1]
+  g = torch.Generator().manual_seed(300 + seed)
+  xyz = pts[None] + 0.08 * torch.randn(V, Rn, S, 3, generator=g)
+  keep = ~boundary_margin(xyz, scene['src_cameras'][0])
+  cot = torch.randn(Rn, S, V, 3 + Fw, generator=g) * keep[..., None].float()
+  pix, in_front = O.compute_projections(xyz, scene['src_cameras'][0])
+  h, w = (float(x) for x in scene['src_cameras'][0][0][:2])
+  inside = (pix[..., 0] >= 0) & (pix[..., 0] <= w - 1) & (pix[..., 1] >= 0) & (pix[..., 1] <= h - 1) & in_front
+  if name == 'harsh':
+    assert int((~inside).sum()) > 0 and int((~in_front).sum()) > 0, 'the case must put taps outside the image and behind a camera'
+
+  def oracle(dtype, with_maps=maps):
+    cv = lambda t: t.to(dtype)
+    fmr = cv(fm).clone().requires_grad_(with_maps)
+    xr = cv(xyz).clone().requires_grad_(True)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    try:
+      rf = O.compute_with_motions(cv(pts), xr, cv(scene['camera']), cv(scene['src_rgbs']), cv(scene['src_cameras']), fmr)[0]
+      (rf * cv(cot)).sum().backward()
+    finally:
+      torch.set_default_dtype(prev)
+    return dict(maps=fmr.grad, xyz=xr.grad)
+
+  r32, r64 = oracle(torch.float32), oracle(torch.float64)
+  sens = projection_sensitivity(lambda: oracle(torch.float32))  # a tap 1e-6 px across a cell edge changes the slope d/dxyz sees
+  sc = to_dev(scene, device)
+  fm_d = fm.to(device).requires_grad_(maps)
+  xyz_d = xyz.to(device).requires_grad_(True)
+  views = ops.SourceViews(sc['camera'], sc['src_rgbs'], sc['src_cameras'], fm_d.detach())
+  rf, _, mk, pm = TM.gather(views, fm_d, Rn, S, xyz=xyz_d, pts_st=pts.to(device), pix_mask_thresh=1.0)
+  (rf * cot.to(device)).sum().backward()
+  tag = f'GatherFunction {name} S={S} F={Fw} V={V}' + ('' if maps else ' (maps frozen)')
+  worst = _fn_grad_close(xyz_d.grad, r32['xyz'], r64['xyz'], f'{tag} d xyz', 2e-5, 2e-4, extra=SENS_FACTOR * sens['xyz'])
+  if maps:
+    worst = max(worst, _fn_grad_close(fm_d.grad, r32['maps'], r64['maps'], f'{tag} d featmaps', 2e-6, 2e-5, extra=SENS_FACTOR * sens['maps']))
+  else:
+    assert fm_d.grad is None, f'{tag}: the frozen maps received a gradient'
+  return worst
+
+
+def _traj_oracle(coeff, basis, pts, rows, ref):
+  """pts_seq[v] = pts + traj(basis[row_v]) - traj(basis[ref]) (render_ray.py:361-369, :965-985); row < 0 (a virtual view): pts"""
+  B = basis.shape[1]
+  cx, cy, cz = coeff[..., 0:B], coeff[..., B:2 * B], coeff[..., 2 * B:3 * B]
+  t_ref = O.compute_traj_pts(cx, cy, cz, basis[None, None, ref, :])
+  return torch.stack([pts + (O.compute_traj_pts(cx, cy, cz, basis[None, None, r, :]) - t_ref) if r >= 0 else pts for r in rows], 0)
+
+
+def check_trajectory_fn(device, B=6, R=5, S=37, ref=1, offsets=(-3, -2, -1, 0, 1, 2, 3), num_vv=2, nf=24, seed=0):
+  """train_motion.TrajectoryFunction: d pts_seq -> d coefficients, d basis (per-workgroup LDS sums + atomics), d points; k_trajectory_bwd8 for
+  B <= 8, k_trajectory_bwd above.  The rows are (ref + offset) % nf -- with ref near 0 they wrap to the end of the basis -- and num_vv rows of -1
+  (virtual views: undisplaced, no basis gradient)."""
+  from dynibar_amd import train_motion as TM
+  g = torch.Generator().manual_seed(400 + seed)
+  rows = [(ref + o) % nf for o in offsets] + [-1] * num_vv
+  assert any(ref + o < 0 or ref + o >= nf for o in offsets), 'the case must wrap a row modulo the frame count'
+  coeff = 0.3 * torch.randn(R, S, 3 * B, generator=g)
+  basis = O.init_dct_basis(B, nf) + 0.05 * torch.randn(nf, B, generator=g)
+  pts = torch.randn(R, S, 3, generator=g)
+  cot = torch.randn(len(rows), R, S, 3, generator=g)
+
+  def oracle(dtype):
+    c, b, p = (x.to(dtype).clone().requires_grad_(True) for x in (coeff, basis, pts))
+    (_traj_oracle(c, b, p, rows, ref) * cot.to(dtype)).sum().backward()
+    return dict(coeff=c.grad, basis=b.grad, pts=p.grad)
+
+  r32, r64 = oracle(torch.float32), oracle(torch.float64)
+  c, b, p = (x.to(device).requires_grad_(True) for x in (coeff, basis, pts))
+  seq = TM.trajectory_points(c, b, p, rows, ref)
+  assert_close(seq, _traj_oracle(coeff.double(), basis.double(), pts.double(), rows, ref), 1e-6, 1e-6, f'TrajectoryFunction B={B} values')
+  (seq * cot.to(device)).sum().backward()
+  tag = f'TrajectoryFunction B={B} R={R} S={S} rows={rows}'
+  worst = 0.0
+  for k, got in (('coeff', c.grad), ('basis', b.grad), ('pts', p.grad)):
+    worst = max(worst, _fn_grad_close(got, r32[k], r64[k], f'{tag} d {k}', 2e-6, 2e-5))
+  unused = [i for i in range(nf) if i not in rows and i != ref]
+  assert float(cpu(b.grad)[unused].abs().max()) == 0.0, f'{tag}: basis rows no view uses received a gradient'
+  return worst
+
+
+def check_render_flows_fn(device, name='stress', S=64, R=5, V=None, seed=0):
+  """train_motion.RenderFlowsFunction: d flows -> d weights (the cotangent of the compositing weights: the flow loss's route to both nets and
+  the static maps) and d displaced points (k_render_flows_bwd: one wavefront per ray, lanes striding over the samples) vs fp64 autograd through
+  O.compute_optical_flow.  S below, at and above one wavefront, R not a multiple of the four rays of a workgroup."""
+  from dynibar_amd import train_motion as TM
+  scene, o, d, _, _ = cases.scene_case(name)
+  cams = scene['src_cameras'] if V is None else scene['src_cameras'][:, :V].contiguous()
+  Vn = cams.shape[1]
+  g = torch.Generator().manual_seed(500 + seed)
+  Rn = R
+  o, d = o[:1].repeat(Rn, 1), d[:1] + 0.05 * torch.randn(Rn, 3, generator=g)  # rays fanned out around the scene's first
+  near, far = (float(x) for x in scene['depth_range'].reshape(-1)[:2])
+  z = near + (far - near) * torch.sort(torch.rand(Rn, S, generator=g), dim=1).values
+  pts = o[:, None, :] + z[..., None] * d[:, None, :]
+  seq = pts[None] + 0.05 * torch.randn(Vn, Rn, S, 3, generator=g)
+  wts = torch.rand(Rn, S, generator=g)
+  wts = wts / wts.sum(dim=1, keepdim=True)
+  uv = 40.0 * torch.rand(Rn, 2, generator=g)
+  cot = torch.randn(Vn, Rn, 2, generator=g)
+
+  def oracle(dtype):
+    w, q = wts.to(dtype).clone().requires_grad_(True), seq.to(dtype).clone().requires_grad_(True)
+    f = O.compute_optical_flow(w, q, cams.to(dtype), uv.to(dtype))
+    (f * cot.to(dtype)).sum().backward()
+    return f.detach(), dict(weights=w.grad, pts_seq=q.grad)
+
+  (f32, r32), (f64, r64) = oracle(torch.float32), oracle(torch.float64)
+  views = ops.SourceViews(scene['camera'].to(device), scene['src_rgbs'][:, :Vn].contiguous().to(device), cams.to(device),
+                          scene['featmaps'][:Vn].contiguous().to(device))
+  w_d, q_d = wts.to(device).requires_grad_(True), seq.to(device).requires_grad_(True)
+  flows = TM.render_flows(w_d, q_d, views.proj, uv.to(device))
+  tag = f'RenderFlowsFunction {name} V={Vn} R={Rn} S={S}'
+  assert_close(flows, f64, 2e-4, 1e-5, f'{tag} flows', extra=3.0 * (f32.double() - f64).abs())
+  (flows * cot.to(device)).sum().backward()
+  worst = _fn_grad_close(w_d.grad, r32['weights'], r64['weights'], f'{tag} d weights', 2e-5, 2e-4)
+  return max(worst, _fn_grad_close(q_d.grad, r32['pts_seq'], r64['pts_seq'], f'{tag} d pts_seq', 2e-5, 2e-4))
+
+
+def check_motion_mlp_fn(device, name='few', S=16, R=3, sf_mag_div=1.0, weights='init', seed=0):
+  """train_motion.MotionMLPFunction: d coeff -> d every MotionMLP parameter and d points vs fp64 autograd through O.motion_mlp with the
+  reference's tail zeroing raw_coeff[:, -n_last:, :] *= 0, n_last = round(0.1 S) (render_ray.py:684).  For S <= 4 n_last is 0 and the
+  reference's [-0:] zeroes EVERY sample: the renderer asks for n_zero = S then (render_ray._dual_branch), and all gradients vanish."""
+  from dynibar_amd import train_motion as TM
+  scene, o, d, _, _ = cases.scene_case(name)
+  o, d = o[:R], d[:R]
+  pts = O.sample_along_camera_ray(o, d, scene['depth_range'], S, True, True)[0]
+  Rn = pts.shape[0]
+  sd = O.tdict(_weights(weights)['motion_mlp'])
+  t = torch.tensor([0.37])
+  n_last = int(round(S * 0.1))
+  g = torch.Generator().manual_seed(600 + seed)
+  cot = torch.randn(Rn, S, 3 * cases.NUM_BASIS, generator=g)
+
+  def oracle(dtype):
+    w = {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
+    p = pts.to(dtype).clone().requires_grad_(True)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    try:
+      x = torch.cat([p, t.to(dtype)[None, None, :].expand(Rn, S, 1)], -1)
+      coeff = O.motion_mlp(w, x, sf_mag_div=sf_mag_div)
+      keep = torch.ones(Rn, S, 1, dtype=dtype)
+      keep[:, -n_last:, :] = 0.0  # the reference's slice, [-0:] included
+      coeff = coeff * keep
+      (coeff * cot.to(dtype)).sum().backward()
+    finally:
+      torch.set_default_dtype(prev)
+    return coeff.detach(), dict({k: v.grad for k, v in w.items()}, pts=p.grad)
+
+  (c32, r32), (c64, r64) = oracle(torch.float32), oracle(torch.float64)
+  prm = {k: v.to(device).requires_grad_(True) for k, v in sd.items()}
+  p_d = pts.to(device).requires_grad_(True)
+  coeff = TM.motion_coeff(prm, p_d, t.to(device), n_last if n_last > 0 else S, sf_mag_div)
+  tag = f'MotionMLPFunction {name} R={Rn} S={S} (n_last {n_last}) sf_mag_div={sf_mag_div}'
+  assert_close(coeff, c64, 2e-5, 1e-4, f'{tag} coefficients', extra=3.0 * (c32.double() - c64).abs())
+  (coeff * cot.to(device)).sum().backward()
+  got = dict({k: v.grad for k, v in prm.items()}, pts=p_d.grad)
+  if n_last == 0:  # every sample zeroed: nothing flows back
+    for k, v in got.items():
+      assert v is not None and float(r64[k].abs().max()) == 0.0 and float(cpu(v).abs().max()) == 0.0, f'{tag}: gradient of {k} must vanish'
+    return 0.0
+  gmax = max(float(v.abs().max()) for k, v in r64.items() if k != 'pts')
+  worst = 0.0
+  for k, ref in r64.items():
+    scale = float(ref.abs().max())
+    cond = 3.0 * (r32[k].double() - ref.double()).abs()
+    assert_close(got[k], ref.double(), 8e-5 * scale + 8e-7 * gmax, 4e-4, f'{tag} d {k} (max |g| {scale:.2e})', extra=cond)
+    if scale > 1e-3 * gmax:
+      worst = max(worst, float((cpu(got[k]).double() - ref.double()).abs().max()) / scale)
+  return worst

@@ -359,6 +359,62 @@ def test_training_iteration_at_the_training_shape(dev):
   parity.check_train_mono_large(dev)
 
 
+def test_full_training_iteration_at_init_weights(dev, golden_dir):
+  """the same iteration at initialisation-scale weights (tests/golden/mono_train_grad_init.npz), where the densities do not saturate: the flow
+  term's route through the compositing weights to both nets and the static maps (k_render_flows_bwd's d weights) is live"""
+  n = parity.check_train_mono(dev, _golden(golden_dir, 'mono_train_grad_init.npz'), weights='init')
+  assert n > 300
+
+
+def test_training_iteration_at_the_training_shape_at_init_weights(dev):
+  parity.check_train_mono_large(dev, weights='init')
+
+
+@pytest.mark.parametrize('terms', ['full', 'flow'])
+@pytest.mark.parametrize('pattern', list(parity.FREEZE_PATTERNS))
+def test_training_a_subset_of_the_model(dev, golden_dir, pattern, terms):
+  """a fine-tune that freezes part of the model (requires_grad_(False) on nets / the basis, feature maps without grad): the kernels are chosen by
+  which inputs carry a graph, and every selection must give the trainable leaves the reference's gradients and the frozen ones none"""
+  parity.check_train_mono_frozen(dev, parity.FREEZE_PATTERNS[pattern], terms, _golden(golden_dir, 'mono_train_grad_init.npz'))
+
+
+def test_grad_mode_with_nothing_trainable_matches_no_grad(dev):
+  """grad mode with every leaf frozen runs the inference kernels: outputs bitwise equal to the torch.no_grad() run, a loss without grad_fn"""
+  assert parity.check_train_mono_nothing_trainable(dev) > 30
+
+
+# ---- the motion path's autograd Functions one by one (dynibar_amd/train_motion.py) vs fp64 autograd through the oracle ----------------------
+@pytest.mark.parametrize('kw', [dict(name='few', S=16), dict(name='harsh', S=4), dict(name='harsh', S=64), dict(name='few', S=8, F=16),
+                                dict(name='small', S=48, F=16), dict(name='harsh', S=8, maps=False), dict(name='stress', S=32, F=16, maps=False)])
+def test_gather_function(dev, kw):
+  """GatherFunction w.r.t. the feature maps and the displaced points: k_gather_bwd32_ray (F = 32, S >= 8) / k_gather_bwd32 / k_gather_bwd (F = 16),
+  k_gather_bwd_pts32 / k_gather_bwd_pts; taps outside the image and behind a camera; the points alone requiring grad"""
+  parity.check_gather_fn(dev, **kw)
+
+
+@pytest.mark.parametrize('kw', [dict(B=6), dict(B=6, R=70, S=64, seed=1), dict(B=10, ref=22, offsets=(-2, -1, 0, 1, 2, 3)),
+                                dict(B=10, R=70, S=64, ref=0, offsets=(-3, -1, 0, 2), num_vv=3, seed=1), dict(B=8, R=9, S=29, ref=23, offsets=(-1, 0, 1))])
+def test_trajectory_function(dev, kw):
+  """TrajectoryFunction: k_trajectory_bwd8 (B <= 8) and k_trajectory_bwd (B = 10), several workgroups; rows wrapping modulo the frame count,
+  virtual-view rows of -1"""
+  parity.check_trajectory_fn(dev, **kw)
+
+
+@pytest.mark.parametrize('S', [1, 63, 64, 65, 200])
+@pytest.mark.parametrize('R,V', [(5, 1), (7, 16), (130, 16)])
+def test_render_flows_function(dev, S, R, V):
+  """RenderFlowsFunction: d weights (the flow loss's route to the nets and the static maps) and d displaced points; one wavefront per ray, its
+  lanes striding over rays shorter than, as long as and longer than 64 samples; ray counts that do not fill the last workgroup"""
+  parity.check_render_flows_fn(dev, S=S, R=R, V=V)
+
+
+@pytest.mark.parametrize('kw', [dict(S=3), dict(S=4), dict(S=16, sf_mag_div=2.5), dict(S=64, R=5), dict(name='small', S=48, R=6, sf_mag_div=0.7),
+                                dict(S=16, weights='trained')])
+def test_motion_mlp_function(dev, kw):
+  """MotionMLPFunction: every parameter and the points; S <= 4 (n_last rounds to 0 and the reference zeroes every sample), sf_mag_div != 1"""
+  parity.check_motion_mlp_fn(dev, **kw)
+
+
 @pytest.mark.parametrize('name', ['small', 'harsh', 'noise'])
 def test_gather_and_passes_from_the_reference_matrices(dev, golden_dir, name):
   """With the reference's own fp32 K.inv(c2w) handed in (Projector(matrix_mode=...) / SourceViews(proj_matrices=...)) nothing separates the gather from

@@ -223,9 +223,28 @@ def test_static_bootstrap_gradients(golden_dir, kid):
 def test_mono_train_gradients(golden_dir, lname):
   """Section 8(f)3: torch autograd through the oracle's render_rays_mono_train + the restated train.py loss against the REAL reference's
   autograd (digests of every gradient): pins the gradients the GPU tests hold the HIP backward kernels to."""
+  _mono_train_gradients(load(golden_dir, 'mono_train_grad.npz'), lname, 'trained')
+
+
+@pytest.mark.parametrize('lname', ['full', 'flow', 'cycle'])
+def test_mono_train_gradients_at_init_weights(golden_dir, lname):
+  """The same at the initialisation-scale weights of cases.model_weights(0) (tests/golden/mono_train_grad_init.npz).  At trained scale the
+  densities saturate and the flow term's route through the compositing weights to the nets and the static maps is ~1e-10 of its size; here
+  it is live."""
+  _mono_train_gradients(load(golden_dir, 'mono_train_grad_init.npz'), lname, 'init')
+
+
+def test_mono_train_init_golden_keeps_the_flow_route_live(golden_dir):
+  """Liveness guard of the init-weights golden: the flow term's gradient of DynibarStatic (reached only through the compositing weights) must
+  be at least 1e-2 of the full loss's.  A case moved into saturation fails here instead of silently testing a zero."""
+  g = load(golden_dir, 'mono_train_grad_init.npz')
+  amax = lambda lname: max(float(v[0]) for k, v in g.items() if k.startswith(f'{lname}/net_coarse_st.') and k.endswith('/absmax'))
+  assert amax('flow') >= 1e-2 * amax('full'), f'net_coarse_st: flow-term gradient {amax("flow"):.2e} vs full {amax("full"):.2e}'
+
+
+def _mono_train_gradients(g, lname, weights):
   import parity
-  g = load(golden_dir, 'mono_train_grad.npz')
-  loss, grads = parity.oracle_mono_train_step(cases.MONO_TRAIN_LOSSES[lname])
+  loss, grads = parity.oracle_mono_train_step(cases.MONO_TRAIN_LOSSES[lname], weights=weights)
   close(loss, g[f'{lname}/loss'], rtol=1e-5, atol=1e-7)
   n = 0
   gmax = max(float(v[0]) for k, v in g.items() if k.startswith(lname + '/') and k.endswith('/absmax') and '/featmaps' not in k)  # round-off floor of the small tensors
