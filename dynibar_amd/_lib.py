@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get('DYNIBAR_HIP_LIB') or os.path.join(_HERE, 'csrc', 'lib
 
 _CTYPES = {
     'int': ctypes.c_int, 'float': ctypes.c_float, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
-    'size_t': ctypes.c_size_t, 'void': None, 'long': ctypes.c_long, 'unsigned': ctypes.c_uint,
+    'size_t': ctypes.c_size_t, 'void': None, 'long': ctypes.c_long, 'unsigned': ctypes.c_uint, 'double': ctypes.c_double,
 }
 
 

@@ -37,7 +37,8 @@ static const char* const g_prof_names[DYN_K_COUNT] = {
     "k_dynamic_views", "k_dynamic_points", "k_motion_mlp", "k_trajectory_points", "k_render_flows", "k_expected_scene_flow", "k_image_rays",
     "k_static_points_qkv", "k_dynamic_points_qkv", "k_enc_conv7", "k_enc_conv3", "k_enc_conv1", "k_enc_block_out",
     "k_train_gemm", "k_train_rows", "k_train_attn", "k_gather_bwd", "k_motion_zero_tail", "k_ragged_plan",
-    "k_splat_project", "k_splat_keys", "k_splat_sort", "k_splat_resolve", "k_sobel_alpha", "k_vv_finish"};
+    "k_splat_project", "k_splat_keys", "k_splat_sort", "k_splat_resolve", "k_sobel_alpha", "k_vv_finish",
+    "k_objective_fwd", "k_objective_bwd"};
 
 static void prof_flush(int slot) {
   for (int i = 0; i < g_prof.used[slot]; ++i) {

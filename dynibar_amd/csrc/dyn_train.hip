@@ -3010,3 +3010,6 @@ extern "C" int dyn_train_zero_tail(float* x, long R, int S, int C, int n_last, f
              C, n_last, scale);
   return 0;
 }
+
+// the training objective of the monocular main loop and eff_distloss_native (train.py:300-456)
+#include "dyn_objective.h"

@@ -574,6 +574,70 @@ int dyn_sobel_alpha(const float* x, int B, int H, int W, float beta, float* alph
  * uint8(255 clip(clip(rgb / 255, 0, 1) m, 0, 1)), m = erosion(clip(alpha, 0, 1) > 0.5, disk(1)); out-of-image neighbours do not erode */
 int dyn_vv_finish(const float* feat, int B, int C, int H, int W, uint8_t* out, void* stream);
 
+/* ====== the training objective of the monocular main loop (train.py:300-456) on the dictionary render_rays_mono(is_train=True) returns =====
+ * Forward: k_objective_rays (one wavefront per ray: the Charbonnier colour terms, disparity, flow, sum_S weights_dy / weights_st -> ratio ->
+ * entropy and the static mask, the distortion loss by two wave scans) and k_objective_samples (one thread per sample: consistency and the
+ * three scene-flow regularisers) store per-workgroup partial sums (double, plain stores, every entry written); k_objective_finish adds them in
+ * a fixed order and forms the nine logged scalars.  No float atomics anywhere: two calls on the same inputs give the same bits.
+ * Backward: element-wise given the forward's sums (k_objective_rays_bwd, k_objective_samples_bwd); grad_loss is read from device memory.
+ * Conventions as torch has them: sign(0) = 0, clamp(min=c) passes the gradient where x >= c.  Everything the reference detaches
+ * (occ_weights, occ_weight_map, the static mask's 1 - ratio factor and its < 0.1 mask) receives no gradient.
+ * Per-ray and per-sample arithmetic is double: the result is the float64 value of the formulas on the fp32 inputs, rounded once.
+ * Workspace: DEVICE scratch of dyn_objective_workspace_bytes(R, S) bytes (0: unsupported shape); the backward reads what the forward left. */
+#define DYN_OBJECTIVE_LOGGED 9  /* loss, rgb, cycle, flow, disp, reg, entropy, distortion, static */
+size_t dyn_objective_workspace_bytes(int R, int S);
+typedef struct {
+  int R, S;                  /* rays, samples per ray (S >= 2) */
+  int T;                     /* frames of pts_traj_* (0: no consistency term) */
+  int NV;                    /* flow views, 0..6 */
+  /* supervision (ray_batch) */
+  const float *t_rgb;        /* [R,3] */
+  const float *t_disp;       /* [R] */
+  const float *t_flows;      /* [>=NV,R,2] */
+  const float *t_masks;      /* [>=NV,R,1] */
+  const float *motion_mask, *static_mask;  /* [R] */
+  /* outputs_coarse_ref */
+  const float *rgb_ref, *rgb_dy, *rgb_static;  /* [R,3] */
+  const float *depth;        /* [R] */
+  const float *render_flows; /* [NV,R,2] */
+  const float *weights, *weights_dy, *weights_st, *s_vals;  /* [R,S] */
+  const uint8_t *mask_ref;   /* [R] (torch.bool) */
+  /* outputs_coarse_ref_dy, outputs_coarse_anchor, outputs_coarse_anchor_dy */
+  const float *rgb_ref_dy, *rgb_anc, *rgb_anc_dy;  /* [R,3] */
+  const float *owm_anc, *owm_anc_dy;  /* [R] occ_weight_map */
+  const uint8_t *mask_ref_dy, *mask_anc, *mask_anc_dy;  /* [R] */
+  const float *pts_traj_ref, *pts_traj_anchor;  /* [T,R,S,3], NULL: the consistency term is not evaluated */
+  const float *occ_weights;  /* [R,S] */
+  const float *sf_seq;       /* [6,R,S,3], NULL: the scene-flow regularisers are not evaluated */
+  /* weights of the terms with the schedule applied (0: the term is left out and logs 0) */
+  double k_rgb;              /* Criterion(ref) + temporal(anchor) */
+  double k_rgb_dyn;          /* the dynamic-only term: 1 while epoch < init_decay_epoch */
+  double k_rgb_dy;           /* the two _dy terms: 10 ** -divisor */
+  double w_disp, w_flow, w_cycle, w_reg, w_entropy, w_distortion;
+  double k_static;           /* the adaptive static term */
+  double k_static2;          /* its divisor > 4 addition: 0.1 */
+  void* workspace;
+  size_t workspace_bytes;
+} DynObjectiveParams;
+/* loss [1], logged [DYN_OBJECTIVE_LOGGED]: device floats */
+int dyn_objective_fwd(const DynObjectiveParams* p, float* loss, float* logged, void* stream);
+typedef struct {             /* cotangents; NULL: not wanted, not computed.  Every element of a non-NULL tensor is written once. */
+  const float* grad_loss;    /* [1] device */
+  float *rgb_ref, *rgb_dy, *rgb_static, *rgb_ref_dy, *rgb_anc, *rgb_anc_dy, *depth, *render_flows, *weights, *weights_dy, *weights_st;
+  float *pts_traj_ref, *pts_traj_anchor, *sf_seq;
+} DynObjectiveGrads;
+int dyn_objective_bwd(const DynObjectiveParams* p, const DynObjectiveGrads* g, void* stream);
+
+/* eff_distloss_native of torch_efficient_distloss (the O(S) form of the mip-NeRF-360 distortion loss): per ray
+ * (1/3) sum_i interval_i w_i^2 + 2 sum_{i>=1} (w_i m_i sum_{j<i} w_j - w_i sum_{j<i} w_j m_j), then the mean over the R rays.
+ * w, m, interval: [R,S] rows of stride ld_* floats (unit stride along S).  partial: DEVICE scratch of dyn_distloss_partials(R) doubles. */
+long dyn_distloss_partials(long R);
+int dyn_distloss_fwd(const float* w, long ld_w, const float* m, long ld_m, const float* interval, long ld_i, long R, int S, double* partial,
+                     float* loss, void* stream);
+/* dw / dm / dinterval [R,S] contiguous, NULL: not wanted */
+int dyn_distloss_bwd(const float* w, long ld_w, const float* m, long ld_m, const float* interval, long ld_i, long R, int S, const float* grad_loss,
+                     float* dw, float* dm, float* dinterval, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
