@@ -194,15 +194,24 @@ __global__ void __launch_bounds__(ENC_THREADS, 2) k_enc_conv(ConvArgs p) {
 
   const int tiles_x = (p.Wout + 31) / 32;
   const long n_tiles = (r_hi - r_lo) * tiles_x;
-  float s1[2][16], s2[2][16];  // this lane's running per-channel sums of what it wrote (channel 32 t + fi(r, h)) for image n_cur
+  // This lane's running per-channel sums of what it wrote (channel 32 t + fi(r, h)) for image n_cur, taken ABOUT A PIVOT: s1 = sum (x - pv),
+  // s2 = sum (x - pv)^2 with pv the channel's value at the first pixel the wave wrote for this image (the same for the 32 lanes of a half).
+  // fp32 sums of x and x * x lose the variance of a channel whose mean is far from zero in units of its spread (a dim or foggy frame: |mean| / std
+  // of a conv1 channel in the hundreds; relative error of var = E[x^2] - mean^2 about (mean / std)^2 * 2^-24 * the growth of the sum); about the pivot
+  // the summands are of the size of the spread, and the shift back to sum x, sum x^2 is done in double when the sums are flushed.
+  float s1[2][16], s2[2][16], pv[2][16];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { s1[t][r] = 0.f; s2[t][r] = 0.f; }
-  int n_cur = -1;
+    for (int r = 0; r < 16; ++r) { s1[t][r] = 0.f; s2[t][r] = 0.f; pv[t][r] = 0.f; }
+  int n_cur = -1, cnt = 0;   // cnt: pixels this lane added since the last flush
+  bool have_pv = false;      // (wave-uniform)
   // the 32 pixel-lanes of a half hold partial sums of the same 32 channels: butterfly over the lanes, then one fp64 atomic per channel
   auto flush_stats = [&]() {
     if (p.stats_out == nullptr || n_cur < 0) return;
+    int k = cnt;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) k += __shfl_xor(k, m);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -212,11 +221,14 @@ __global__ void __launch_bounds__(ENC_THREADS, 2) k_enc_conv(ConvArgs p) {
         for (int m = 16; m >= 1; m >>= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
         if (j == 0) {
           double* st = p.stats_out + ((long)n_cur * 64 + 32 * t + dyn_fi(r, h)) * 2;
-          atomicAdd(st, (double)a);
-          atomicAdd(st + 1, (double)b);
+          const double pd = (double)pv[t][r], ad = (double)a, kd = (double)k;
+          atomicAdd(st, ad + kd * pd);                                 // sum x = sum (x - pv) + k pv
+          atomicAdd(st + 1, (double)b + pd * (2.0 * ad + kd * pd));    // sum x^2 = sum (x - pv)^2 + 2 pv sum (x - pv) + k pv^2
         }
         s1[t][r] = 0.f; s2[t][r] = 0.f;
       }
+    cnt = 0;
+    have_pv = false;
   };
 
   for (long tile = wave; tile < n_tiles; tile += ENC_THREADS / 64) {
@@ -258,18 +270,26 @@ __global__ void __launch_bounds__(ENC_THREADS, 2) k_enc_conv(ConvArgs p) {
     if constexpr (CIN == 3) {
       // K = (ky, [kx, ic] padded to 24): this lane's 8 values of group g are k = 16 g + 8 h + e, i.e. 8-float chunk c = 2 g + h of the padded
       // rows: kernel row ky = c / 3, floats [8 (c % 3), + 8) of that row's 21 (+ 3 zero-weight) floats.  Group g + 1 is in flight under group g.
+      // The images enter relative to a pivot colour (the image's own first pixel).  Reflect padding maps a constant image to a constant, so this
+      // shifts every output channel of the image by a constant, which the InstanceNorm that follows removes exactly -- while the products the
+      // engine forms are then of the size of the image's contrast, not of its brightness: on a dim or foggy frame (contrast of a few percent about
+      // mid-grey) the rounding of the products is otherwise tens of times the channel's spread after normalisation.
+      const float piv[3] = {inb[0], inb[1], inb[2]};
       auto load_group = [&](int g, float (&v)[8]) {
         const int c = 2 * g + h;
         const int ky = (c * 11) >> 5;          // c / 3 for c < 32
         const int j0 = (c - 3 * ky) * 8;
         const int iy = reflect_idx(oy * STRIDE + (ky < 7 ? ky : 6) - PAD, p.Hin);
+        // element e of the chunk is input channel (j0 + e) % 3 = (rot + e) % 3: the pivot colour rotated once per chunk, indexed at compile time
+        const int m = c - 3 * ky;  // j0 / 8: rot = j0 % 3 = 0, 2, 1
+        const float q[3] = {m == 0 ? piv[0] : m == 1 ? piv[2] : piv[1], m == 0 ? piv[1] : m == 1 ? piv[0] : piv[2], m == 0 ? piv[2] : m == 1 ? piv[1] : piv[0]};
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const int jj = j0 + e;
           const int kx = (jj * 11) >> 5;        // jj / 3 for jj < 32
           const int ic = jj - 3 * kx;
           const int ix = reflect_idx(oxc * STRIDE + (kx < 7 ? kx : 6) - PAD, p.Win);
-          const float x = inb[((long)iy * p.Win + ix) * 3 + ic];
+          const float x = inb[((long)iy * p.Win + ix) * 3 + ic] - q[e % 3];
           v[e] = (ky < 7 && jj < 21) ? x : 0.f;
         }
       };
@@ -342,8 +362,26 @@ __global__ void __launch_bounds__(ENC_THREADS, 2) k_enc_conv(ConvArgs p) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)  // registers 4 q .. 4 q + 3 are channels 8 q + 4 h + (0..3) of the tile
           *reinterpret_cast<float4*>(o + 8 * q + 4 * h) = make_float4(acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]);
+      }
+    }
+    if (p.stats_out != nullptr) {
+      if (!have_pv) {  // the first tile of this image in this wave: lane 0 of each half (always a live pixel) gives the pivots
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { s1[t][r] += acc[t][r]; s2[t][r] = fmaf(acc[t][r], acc[t][r], s2[t][r]); }
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) pv[t][r] = __shfl(acc[t][r], lane & 32);
+        have_pv = true;
+      }
+      if (live) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float d = acc[t][r] - pv[t][r];
+            s1[t][r] += d;
+            s2[t][r] = fmaf(d, d, s2[t][r]);
+          }
+        ++cnt;
       }
     }
   }
@@ -586,7 +624,7 @@ extern "C" int dyn_enc_im2col(const float* in, int N, int Hin, int Win, int C, i
   if (int rc = enc_geom_check(q, "dyn_enc_im2col")) return rc;
   DYN_REQUIRE((ldc & 3) == 0 && ((uintptr_t)col & 15) == 0 && ((C & 3) != 0 || ((uintptr_t)in & 15) == 0),
               "dyn_enc_im2col: ldc a multiple of 4 floats, 16-byte-aligned patch matrix (and map, when C is a multiple of 4)");
-  if ((C & 3) != 0) {
+  if ((C & 3) != 0 || ldc != (long)KH * KW * C) {  // (the float4 form below copies the taps only: padding columns need the general one)
     const long total4 = (long)N * Hout * Wout * (ldc / 4);
     DYN_LAUNCH(DYN_K_ENC_BLOCK, "dyn_enc_im2col", k_enc_im2col_any, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, in, col, ldc);
     return 0;
@@ -609,22 +647,33 @@ extern "C" int dyn_enc_col2im(const float* dcol, long ldc, int N, int Hin, int W
 #define ENC_IN_CHUNK 256  // pixels per block: 18 quarter-resolution maps give 648 blocks (1024 left a third of the CUs idle)
 // stats[n][c] = {sum x, sum x^2} (fp64, zeroed by the caller)
 __global__ void __launch_bounds__(256) k_enc_in_stats(const float4* __restrict__ x, long HW, double* __restrict__ stats) {
-  float* red = reinterpret_cast<float*>(dyn_smem);  // [16 pixel lanes][64 ch][2]
+  double* red = reinterpret_cast<double*>(dyn_smem);  // [16 pixel lanes][64 ch][2]
   const int n = blockIdx.y, g = threadIdx.x & 15, pl = threadIdx.x >> 4;
   const long p0 = (long)blockIdx.x * ENC_IN_CHUNK, p1 = p0 + ENC_IN_CHUNK < HW ? p0 + ENC_IN_CHUNK : HW;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s;
+  // fp32 sums about a pivot (the thread's first value), shifted back to sum x, sum x^2 in double: see k_enc_conv
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s, pv = s;
+  int cnt = 0;
   for (long p = p0 + pl; p < p1; p += 16) {
     const float4 v = x[((long)n * HW + p) * 16 + g];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    s2.x += v.x * v.x; s2.y += v.y * v.y; s2.z += v.z * v.z; s2.w += v.w * v.w;
+    if (cnt == 0) pv = v;
+    const float4 d = make_float4(v.x - pv.x, v.y - pv.y, v.z - pv.z, v.w - pv.w);
+    s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
+    s2.x = fmaf(d.x, d.x, s2.x); s2.y = fmaf(d.y, d.y, s2.y); s2.z = fmaf(d.z, d.z, s2.z); s2.w = fmaf(d.w, d.w, s2.w);
+    ++cnt;
   }
-  float* r = red + (pl * 64 + 4 * g) * 2;
-  r[0] = s.x; r[1] = s2.x; r[2] = s.y; r[3] = s2.y; r[4] = s.z; r[5] = s2.z; r[6] = s.w; r[7] = s2.w;
+  double* r = red + (pl * 64 + 4 * g) * 2;
+  const double kd = (double)cnt;
+  auto put = [&](int e, float p_, float a_, float b_) {
+    const double pd = (double)p_, ad = (double)a_;
+    r[2 * e] = ad + kd * pd;
+    r[2 * e + 1] = (double)b_ + pd * (2.0 * ad + kd * pd);
+  };
+  put(0, pv.x, s.x, s2.x); put(1, pv.y, s.y, s2.y); put(2, pv.z, s.z, s2.z); put(3, pv.w, s.w, s2.w);
   __syncthreads();
   if (threadIdx.x < 128) {
     const int c = threadIdx.x >> 1, k = threadIdx.x & 1;
     double t = 0.0;
-    for (int l = 0; l < 16; ++l) t += (double)red[(l * 64 + c) * 2 + k];
+    for (int l = 0; l < 16; ++l) t += red[(l * 64 + c) * 2 + k];
     atomicAdd(stats + ((long)n * 64 + c) * 2 + k, t);
   }
 }
@@ -753,7 +802,7 @@ __global__ void __launch_bounds__(256) k_enc_in_bwd_apply(const float4* __restri
 static bool enc_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 extern "C" int dyn_enc_in_stats(const float* x, int N, long HW, double* stats, void* stream) {
   DYN_REQUIRE(x && stats && N > 0 && HW > 0 && enc_al16(x), "dyn_enc_in_stats: bad arguments");
-  DYN_LAUNCH(DYN_K_ENC_BLOCK, "dyn_enc_in_stats", k_enc_in_stats, dim3((unsigned)((HW + ENC_IN_CHUNK - 1) / ENC_IN_CHUNK), N), dim3(256), 16 * 64 * 2 * 4,
+  DYN_LAUNCH(DYN_K_ENC_BLOCK, "dyn_enc_in_stats", k_enc_in_stats, dim3((unsigned)((HW + ENC_IN_CHUNK - 1) / ENC_IN_CHUNK), N), dim3(256), 16 * 64 * 2 * sizeof(double),
              (hipStream_t)stream, reinterpret_cast<const float4*>(x), HW, stats);
   return 0;
 }

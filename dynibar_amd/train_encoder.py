@@ -117,6 +117,10 @@ def _forward(w, img):
   s = {}
   c1 = _Conv(w['conv1.weight'], 7, 2, 3)
   n1 = _Norm(w['bn1.weight'], w['bn1.bias'])
+  # The images enter relative to a pivot colour, each image's own first pixel, as in k_enc_conv: with reflect padding that shifts every channel of
+  # conv1's output by a constant per image, which bn1 (InstanceNorm) removes exactly, forward and backward (the gradient w.r.t. conv1's output sums
+  # to zero over an image) -- and the products are of the size of the image's contrast instead of its brightness (a dim frame: 20x smaller).
+  img = img - img[:, :1, :1, :]
   a0 = c1.fwd(st, img)
   x = n1.fwd(st, a0, relu=True)
   s['stem'] = (c1, n1, a0, x)

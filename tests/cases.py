@@ -113,11 +113,32 @@ def anchor_case(scene, num_vv=2, anchor_shift=1):
   return sc, (fidx, aidx), (temb, temb_a), (toff, aoff)
 
 
-def encoder_case(name='small'):
-  """Seeded image batch [N,H,W,3] in [0,1] for the feature encoder (the data loaders' source images) and the encoder weights."""
-  cfg = {'small': dict(seed=11, N=2, H=40, W=56), 'odd': dict(seed=12, N=3, H=37, W=50), 'wide': dict(seed=13, N=1, H=64, W=160),
-         'tiny': dict(seed=14, N=2, H=21, W=30)}[name]  # tiny: the emulator's training-form case (no golden)
+ENCODER_CASES = {
+    'small': dict(seed=11, N=2, H=40, W=56), 'odd': dict(seed=12, N=3, H=37, W=50), 'wide': dict(seed=13, N=1, H=64, W=160),
+    'tiny': dict(seed=14, N=2, H=21, W=30),  # tiny: the emulator's training-form case (no golden)
+    # the shapes the encoder runs in production (eval_nvidia.py: 18 source views; train.py: 10) and shapes chosen for how k_enc_conv splits the
+    # N * Hout output rows over the workgroups (tests/encoder_checks.py:conv_split states what each reaches)
+    'eval': dict(seed=15, N=18, H=288, W=512), 'train': dict(seed=16, N=10, H=288, W=512),
+    'ragged': dict(seed=17, N=7, H=147, W=97), 'just_over': dict(seed=18, N=3, H=201, W=131),
+    'many': dict(seed=19, N=300, H=16, W=16), 'min': dict(seed=20, N=1, H=16, W=16), 'nine': dict(seed=22, N=9, H=16, W=16),
+    'tall': dict(seed=26, N=2, H=64, W=16),
+    'odd_w': dict(seed=21, N=1, H=33, W=45),  # odd width, pinned to the real reference by tests/golden/encoder_odd_w.npz
+    # low-contrast frames (tests/encoder_checks.py:check_encoder_conditioning): |mean| / std of a conv1 channel in the hundreds, or no variance at all
+    'dim': dict(seed=23, N=2, H=288, W=512, contrast=0.05), 'flat': dict(seed=24, N=2, H=288, W=512, noise=0.01),
+    'const': dict(seed=25, N=2, H=288, W=512, noise=0.0),
+}
+
+
+def encoder_case(name='small', shape=None):
+  """Seeded image batch [N,H,W,3] in [0,1] for the feature encoder (the data loaders' source images) and the encoder weights.
+  shape = (N, H, W) overrides the case's size (the emulator runs the low-contrast cases on thumbnails)."""
+  cfg = dict(ENCODER_CASES[name])
+  if shape is not None:
+    cfg['N'], cfg['H'], cfg['W'] = shape
   rng = np.random.default_rng([cfg['seed'], 5])
+  if 'noise' in cfg:  # uniform noise of the given contrast about mid-grey (0: a constant image)
+    img = 0.5 + cfg['noise'] * (rng.uniform(0.0, 1.0, (cfg['N'], cfg['H'], cfg['W'], 3)) - 0.5)
+    return t(img.astype(np.float32)), syn.make_encoder_weights(cfg['seed'])
   yy, xx = np.meshgrid(np.linspace(0, 1, cfg['H']), np.linspace(0, 1, cfg['W']), indexing='ij')
   imgs = []
   for n in range(cfg['N']):
@@ -126,7 +147,10 @@ def encoder_case(name='small'):
     img = np.stack([0.5 + 0.25 * np.sin(fr[c, 0] * xx + ph[c, 0]) * np.cos(fr[c, 1] * yy + ph[c, 1]) + 0.2 * np.sin(fr[c, 2] * (xx + yy) + ph[c, 2])
                     for c in range(3)], -1) + 0.05 * rng.standard_normal((cfg['H'], cfg['W'], 3))
     imgs.append(np.clip(img, 0.0, 1.0))
-  return t(np.stack(imgs, 0).astype(np.float32)), syn.make_encoder_weights(cfg['seed'])
+  imgs = np.stack(imgs, 0)
+  if 'contrast' in cfg:  # the same frame, dim: its contrast about mid-grey reduced
+    imgs = 0.5 + cfg['contrast'] * (imgs - 0.5)
+  return t(imgs.astype(np.float32)), syn.make_encoder_weights(cfg['seed'])
 
 
 def time_args(n_views):

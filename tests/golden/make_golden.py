@@ -341,11 +341,11 @@ def mono_train_goldens():
   print('mono_train', len(out), 'arrays', sum(v.nbytes for v in out.values()) // 1024, 'KiB')
 
 
-def encoder_goldens():
+def encoder_goldens(names=('small', 'odd', 'wide'), fname='encoder.npz'):
   """The reference's ResNet feature encoder (feature_network.py:179-311) on seeded image batches, incl. odd sizes (reflect padding, strides)."""
   FN = ref.feature_network
   out = {}
-  for name in ('small', 'odd', 'wide'):
+  for name in names:
     imgs, sd = cases.encoder_case(name)
     net = FN.ResNet(coarse_out_ch=32, fine_out_ch=32, coarse_only=False)
     own = net.state_dict()
@@ -354,8 +354,13 @@ def encoder_goldens():
     with torch.no_grad():
       xc, xf = net.eval()(imgs.permute(0, 3, 1, 2))
     out[f'{name}/coarse'] = npy(xc); out[f'{name}/fine'] = npy(xf)
-  np.savez_compressed(os.path.join(HERE, 'encoder.npz'), **out)
-  print('encoder', {k: v.shape for k, v in out.items()})
+  np.savez_compressed(os.path.join(HERE, fname), **out)
+  print(fname, {k: v.shape for k, v in out.items()})
+
+
+def encoder_odd_w_golden():
+  """An odd image WIDTH (1 x 33 x 45 -> maps of 9 x 12) in a file of its own: encoder.npz is not regenerated."""
+  encoder_goldens(('odd_w',), 'encoder_odd_w.npz')
 
 
 def mono_kid_goldens():
@@ -621,6 +626,9 @@ if __name__ == '__main__':
   if 'train_static' in sys.argv[1:]:
     train_static_goldens()
     sys.exit(0)
+  if 'encoder_odd_w' in sys.argv[1:]:
+    encoder_odd_w_golden()
+    sys.exit(0)
   if 'encoder' in sys.argv[1:]:
     encoder_goldens()
     sys.exit(0)
@@ -649,6 +657,7 @@ if __name__ == '__main__':
   mono_train_goldens()
   mono_kid_goldens()
   encoder_goldens()
+  encoder_odd_w_golden()
   camera_format_goldens()
   cross_axis_goldens()
   image_goldens(63, 'image_nvi_tail3.npz')

@@ -981,14 +981,15 @@ def encoder_graph_with_masks(p, x, masks=None):
   return x_out[:, :32], x_out[:, -32:], pre_acts
 
 
-def check_encoder_training(device, name='small'):
+def check_encoder_training(device, name='small', spread=False):
   """Training form of the feature encoder (dynibar_amd.train_encoder) against autograd through the oracle's restatement of the reference's
   ResNet (pinned to the reference's own outputs by the encoder golden): the maps, and the gradient of a seeded linear functional of both
   maps w.r.t. every parameter the executed part of ResNet.forward has (feature_network.py:179-311).  ReLU arguments within rounding of zero
   (one or two of 10^5 on a GPU, none under the emulator) make the gradient jump: the reference gradient is taken with the product's own
   ReLU decisions, after checking that they differ from the oracle's only where the oracle's argument is |v| < 1e-5 of the map's scale.
   Also: a ResNet wrapper around a module with trainable parameters takes this path under grad mode and the forward-only kernels under
-  no_grad, with the same values."""
+  no_grad, with the same values.  spread=True: the step is run twice and the run-to-run spread of every gradient (float atomics) is reported and
+  held to the gradient limit."""
   from dynibar_amd import feature_network, train_encoder
   imgs, sd = cases.encoder_case(name)
   g = torch.Generator().manual_seed(3)
@@ -1010,7 +1011,9 @@ def check_encoder_training(device, name='small'):
     flips += int(diff.sum())
     if bool(diff.any()):
       assert float(v[diff].abs().max()) < 1e-5 * float(v.abs().max()), 'a ReLU decision differs from the oracle away from zero'
-  assert flips <= 8, f'{flips} ReLU decisions differ from the oracle'
+  n_args = sum(int(v.numel()) for v in pre_oracle)
+  print(f'  training encoder {name}: {flips} of {n_args} ReLU decisions differ from the oracle ({flips / n_args:.1e} of them; allowed {max(8, int(4.5e-5 * n_args))})')
+  assert flips <= max(8, 4.5e-5 * n_args), f'{flips} of {n_args} ReLU decisions differ from the oracle'
   oc, of, _ = encoder_graph_with_masks(ref_p, x64, masks)
   cot_c, cot_f = torch.randn(oc.shape, generator=g).double(), torch.randn(of.shape, generator=g).double()
   ((oc * cot_c).sum() + (of * cot_f).sum()).backward()
@@ -1029,6 +1032,18 @@ def check_encoder_training(device, name='small'):
     # fp32-class products, fp32 sums in another order (atomics, split reductions): 3e-5 of the tensor's largest gradient + 1e-4 relative
     assert_close(got, ref, 3e-5 * scale + 1e-7, 1e-4, f'training encoder {name} grad {k} (max |g| {scale:.2e})')
     worst = max(worst, float((cpu(got).double() - ref).abs().max()) / max(scale, 1e-30))
+  if spread:  # the identical step again: float atomics (dgamma / dbeta, the GEMM's split sums) may order differently
+    again = {k: w[k].clone().requires_grad_(True) for k in train_encoder.PARAMS}
+    yc, yf = train_encoder.encoder_forward(again, imgs.to(device).permute(0, 3, 1, 2))
+    ((yc * cot_c.float().to(device)).sum() + (yf * cot_f.float().to(device)).sum()).backward()
+    widest = ('', 0.0)
+    for k in train_encoder.PARAMS:
+      scale = float(ref_p[k].grad.abs().max())
+      d = float((cpu(again[k].grad).double() - cpu(dev_p[k].grad).double()).abs().max()) / max(scale, 1e-30)
+      widest = max(widest, (k, d), key=lambda t: t[1])
+      assert_close(again[k].grad, dev_p[k].grad, 3e-5 * scale + 1e-7, 1e-4, f'training encoder {name} grad {k}: run-to-run spread of two identical steps')
+    print(f'  training encoder {name}: run-to-run spread of the gradients at most {widest[1]:.1e} of the tensor maximum ({widest[0] or "none"})')
+    del again, yc, yf
   print(f'  training encoder {name}: {flips} ReLU decision(s) at arguments within rounding of zero differ from the oracle; worst gradient error {worst:.1e} of the tensor maximum')
   # the wrapper: training form under grad mode, forward-only kernels under no_grad, same maps
   class Holder(torch.nn.Module):

@@ -255,10 +255,10 @@ def test_render_rays_mono_virtual_views(dev):
   parity.check_render_rays_mono_vv(dev)
 
 
-@pytest.mark.parametrize('name', ['small', 'odd', 'wide'])
+@pytest.mark.parametrize('name', ['small', 'odd', 'wide', 'odd_w'])
 def test_feature_encoder(dev, golden_dir, name):
   """Section 8(f)1: the ResNet feature encoder as HIP implicit-GEMM convolutions vs the real reference's feature maps."""
-  parity.check_encoder(dev, _golden(golden_dir, 'encoder.npz'), name)
+  parity.check_encoder(dev, _golden(golden_dir, 'encoder_odd_w.npz' if name == 'odd_w' else 'encoder.npz'), name)
 
 
 def test_feature_encoder_feeds_the_gather_in_place(dev):
