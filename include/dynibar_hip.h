@@ -638,6 +638,39 @@ int dyn_distloss_fwd(const float* w, long ld_w, const float* m, long ld_m, const
 int dyn_distloss_bwd(const float* w, long ld_w, const float* m, long ld_m, const float* interval, long ld_i, long R, int S, const float* grad_loss,
                      float* dw, float* dm, float* dinterval, void* stream);
 
+/* ====== frame metrics of the evaluation loop (eval_nvidia.py:201-247 calculate_psnr / calculate_ssim, :383-457 without LPIPS) ==============
+ * One call evaluates M masks (1..8) on one frame.  Preparation (:383-396): valid = ((r + g) + b > 1e-3f) per pixel of pred, in fp32 in
+ * numpy's order of addition; a uint8 target is float(u8) / 255.0f; with apply_valid both images are multiplied by valid -- all bit-exact
+ * against numpy.  The SSIM map is skimage.metrics.structural_similarity's as :242-244 calls it (7 x 7 uniform window, scipy's `reflect`
+ * boundary, sample covariance, C1 = (0.01 R)^2, C2 = (0.03 R)^2, per channel, not cropped) with R = data_range.  Window sums, variances, S
+ * and the masked sums are double, accumulated in a fixed order: k_metrics_tile stores one row of partial sums per tile of 32 x 8 pixels
+ * (plain stores, every entry written), k_metrics_finish adds the rows in a fixed order.  No float atomics: two calls give the same bits,
+ * and a mask's sums do not depend on the other masks of the call.
+ * sums [M][3] (DEVICE doubles): sum((a - b)^2 m), sum(S m), sum(m) over [H,W,3], a / b the prepared pred / target.
+ * Workspace: DEVICE scratch of dyn_frame_metrics_workspace_bytes(H, W, M) bytes, 8-byte aligned (0: unsupported shape -- H or W below 7,
+ * H*W*3 >= 2^31, M outside 1..8). */
+size_t dyn_frame_metrics_workspace_bytes(int H, int W, int M);
+typedef struct {
+  int H, W;
+  int M;                     /* masks evaluated (1..8), the valid mask included when valid_as_mask0 is set */
+  const float* pred;         /* [H,W,3] */
+  const void* target;        /* [H,W,3] fp32, or uint8 when target_is_u8 is set */
+  int target_is_u8;
+  const float* masks;        /* M - valid_as_mask0 masks of fp32 weights (not necessarily 0 / 1); NULL when there is none */
+  long mask_stride;          /* floats from one mask to the next */
+  int mask_channels;         /* 3: [H,W,3]; 1: [H,W], the weight of a pixel applies to its three channels */
+  int apply_valid;           /* multiply both images by valid (:395-396) */
+  int valid_as_mask0;        /* mask 0 is valid itself (the whole-frame numbers of the script, :398) */
+  double data_range;         /* R > 0, finite */
+  double* ssim_map;          /* [H,W,3] or NULL */
+  uint8_t* valid;            /* [H,W] 0 / 1 or NULL */
+  float* pred_out;           /* [H,W,3] or NULL: the prepared images */
+  float* target_out;
+  void* workspace;
+  size_t workspace_bytes;
+} DynFrameMetricsParams;
+int dyn_frame_metrics(const DynFrameMetricsParams* p, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
