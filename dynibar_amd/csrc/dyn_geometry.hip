@@ -1692,8 +1692,21 @@ extern "C" int dyn_composite(const DynCompositeParams* p, void* stream) {
 // ---------------------------------------------------------------------------------------------------------------
 // K4: importance sampling + sorted merge, one lane per ray   (render_ray.py:19-64, :790-821)
 // The cdf is a sequential per-ray prefix sum accumulated in double and rounded to fp32 per element, which is what torch.cumsum
-// does on the CPU, so the inverse-CDF indices reproduce the reference's exactly given the same weights.  Per-ray scratch lives in LDS, interleaved by lane.
+// does on the CPU.  What that buys: given the same weights the cdf equals torch's up to the last bit of the normaliser (torch.sum's
+// bits depend on the CPU's vector width; the total here is the correctly rounded sum), so a knot may differ from the reference's by
+// one ulp and the inverse-CDF indices equal the reference's wherever u does not sit on a knot (within the cdf's own fp32 error of
+// one).  With all-zero weights the two cdfs are the same bits.  tests/parity.py:check_fine_samples_case states and counts the
+// knot ties.  Per-ray scratch lives in LDS, interleaved by lane.
 // ---------------------------------------------------------------------------------------------------------------
+// u_n of sample_pdf(det=True): the bits of torch.linspace(0, 1, N)[n] on the CPU, fp32, for the FMA-capable (AVX2 / AVX512) ATen
+// kernels of the torch build the goldens were made with (2.10): start + step * n below N / 2, end - step * (N - 1 - n) from there
+// on, the latter contracted into ONE fused multiply-add (the product is not rounded).  This unit is built with -ffp-contract=off,
+// so the fused step is written out.  tests/test_ramp_cpu.py holds a restatement of this function to torch.linspace for N = 2..512.
+__device__ __forceinline__ float linspace01(int n, int N) {
+  const float step = 1.0f / (float)(N - 1);
+  return (n < N / 2) ? (float)n * step : fmaf(-step, (float)(N - 1 - n), 1.0f);
+}
+
 __global__ void k_fine_samples(DynFineSampleParams p, int T) {
   float* lds = reinterpret_cast<float*>(dyn_smem);
   const int t = threadIdx.x;
@@ -1737,9 +1750,7 @@ __global__ void k_fine_samples(DynFineSampleParams p, int T) {
     if (p.u != nullptr) {
       u = p.u[(long)r * N + n];
     } else {
-      // torch.linspace(0, 1, N): start + i*step below the midpoint, end - (N-1-i)*step above it
-      float step = 1.0f / (float)(N - 1);
-      u = (n < N / 2) ? ((float)n * step) : (1.0f - step * (float)(N - 1 - n));
+      u = linspace01(n, N);
     }
     // above = #{j < M : cdf_j <= u}  (render_ray.py:38-39 counts with a loop of M compares).  The cdf is non-decreasing (prefix sums of
     // non-negative terms, rounded monotonically), so the count is an upper bound found by bisection: same integer, log2(M) probes.
@@ -1830,8 +1841,7 @@ __global__ void k_sample_pdf(const float* __restrict__ bins, float* __restrict__
     if (u_in != nullptr) {
       u = u_in[(long)r * N + n];
     } else {
-      const float step = 1.0f / (float)(N - 1);
-      u = (n < N / 2) ? ((float)n * step) : (1.0f - step * (float)(N - 1 - n));
+      u = linspace01(n, N);
     }
     int lo_i = 0, hi_i = M;
     while (lo_i < hi_i) {

@@ -203,6 +203,14 @@ def composite(raw_dy, z_vals, pix_mask_dy, raw_static=None, pix_mask_st=None, pe
              rgb_dy=ptr(rgb_dy), depth=ptr(depth), ray_mask=ptr(rmask), weights=ptr(weights), alpha=ptr(alpha),
              alpha_dy=ptr(a_dy), weights_dy=ptr(w_dy), weights_st=ptr(w_st))
   call('dyn_composite', ctypes.byref(p), stream_of(z_vals))
+  if S == 1:
+    # A one-sample ray has no transmittance in the reference: cumprod(...)[:, :-1] is [R,0] and so is ones_like(T[:, 0:1]) (render_ray.py:187-188,
+    # :289-290), so its weights are [R,0] and every sum over the samples is 0.  The kernel's T_0 = 1 gives way to that; alpha and the ray mask stand.
+    weights = new(R, 0)
+    w_dy, w_st = (new(R, 0), new(R, 0)) if w_dy is not None else (None, None)
+    for t in (rgb, depth, rgb_st, rgb_dy):
+      if t is not None:
+        t.zero_()
   return dict(rgb=rgb, rgb_static=rgb_st, rgb_dy=rgb_dy, depth=depth, mask=rmask, weights=weights, alpha=alpha,
               alpha_dy=a_dy, weights_dy=w_dy, weights_st=w_st, z_vals=z_vals)
 

@@ -47,6 +47,8 @@ def scene_case(name):
       'cross_samples': dict(seed=53, H=32, W=48, V=5, n_static=8, smooth=True, R=4),
       'cross_rays_views': dict(seed=54, H=32, W=48, V=5, n_static=3, smooth=True, R=3),
       'cross_rays_samples': dict(seed=55, H=32, W=48, V=5, n_static=8, smooth=True, R=3),
+      # 24 feature maps: 64 % (F / 4) != 0, the width at which dyn_project_gather falls back to its row-order kernel
+      'wide24': dict(seed=9, H=32, W=48, V=5, n_static=6, smooth=True, R=5, F=24),
   }[name]
   return _scene_of(cfg, cfg.pop('R'))
 
@@ -301,3 +303,133 @@ def load_golden(golden_dir, name):
   for p in parts:
     out.update(np.load(p))
   return out
+
+
+# ---- seeded inputs of the per-ray kernels' edge tests (tests/parity.py: check_fine_samples_case, check_composite_case, ...) -----------------
+# (R, S, N) of k_fine_samples: the smallest legal problem, a second workgroup holding one ray, N != S, the largest problem of the 64-ray
+# LDS split (S = 256, N = 64: 143.5 KiB), the 32-ray split (S = 256 with N = 128 / 255)
+FINE_SAMPLE_SHAPES = [(1, 3, 2), (5, 4, 3), (65, 64, 17), (130, 64, 65), (70, 128, 128), (33, 256, 64), (33, 256, 128), (40, 256, 255)]
+FINE_SAMPLE_SHAPE_LARGE = (4099, 64, 64)  # 65 workgroups, the last one holding three rays (device only)
+FINE_SAMPLE_PDF_SHAPES = [(5, 4, 3), (130, 64, 65), (33, 256, 128)]  # the shapes the sample_pdf export is run on
+FINE_WEIGHT_KINDS = ('composite', 'zero', 'onehot03', 'onehot1', 'ends', 'spike', 'dup_depth')
+FINE_U_KINDS = ('u01', 'knots', 'knots_down')
+RAMP_DETECTOR_SHAPES = [(128, 64), (256, 128), (64, 32)]  # (S, N) with S - 2 = 2 (N - 1): every second knot of a uniform cdf is a ramp value
+
+
+def _gen(*key):
+  return torch.Generator().manual_seed(int(np.random.SeedSequence(list(key)).generate_state(1)[0]))
+
+
+def fine_sample_depths(R, S, inv_uniform, seed=0):
+  """Strictly increasing coarse depths [R,S], uniform in disparity or in depth like sample_along_camera_ray's, near / far varying by ray."""
+  g = _gen(seed, R, S, 1)
+  near = 0.5 + 0.2 * torch.rand(R, 1, generator=g)
+  far = 8.0 + 2.0 * torch.rand(R, 1, generator=g)
+  t = torch.arange(S, dtype=torch.float32)[None] / float(S - 1)
+  if inv_uniform:
+    return 1.0 / (1.0 / near + t * (1.0 / far - 1.0 / near))
+  return near + t * (far - near)
+
+
+def fine_sample_weights(kind, R, S, seed=0):
+  """Coarse weights [R,S] of one of FINE_WEIGHT_KINDS ('dup_depth' uses the composite-like weights; the depths carry its edge)."""
+  g = _gen(seed, R, S, 2)
+  w = torch.zeros(R, S)
+  if kind in ('composite', 'dup_depth', 'u01', 'knots', 'knots_down'):  # softplus of 3 N(0,1) logits through the compositing formula
+    a = 1.0 - torch.exp(-torch.nn.functional.softplus(3.0 * torch.randn(R, S, generator=g)))
+    T = torch.cumprod(torch.cat([torch.ones(R, 1), 1.0 - a + 1e-10], dim=1), dim=1)[:, :-1]
+    w = a * T
+  elif kind in ('onehot03', 'onehot1'):  # all mass in one interior sample
+    w[torch.arange(R), torch.randint(1, S - 1, (R,), generator=g)] = 0.3 if kind == 'onehot03' else 1.0
+  elif kind == 'ends':  # mass only at the two samples sample_pdf excludes
+    w[:, 0] = 0.5
+    w[:, -1] = 0.5
+  elif kind == 'spike':
+    w = torch.full((R, S), 1e-12)
+    w[:, S // 2 if S > 3 else 1] = 0.9
+  else:
+    assert kind == 'zero', kind
+  return w.contiguous()
+
+
+def fine_sample_u(kind, R, N, cdf=None, seed=0):
+  """u [R,N] in [0, 1]: 'rand'; 'u01' (a column of 0 and a column of 1 - ulp); 'knots' (values of the given cdf [R,M+1] themselves);
+  'knots_down' (the same values moved one ulp towards 0)."""
+  g = _gen(seed, R, N, 3)
+  u = torch.rand(R, N, generator=g)
+  if kind == 'u01':
+    u[:, 0] = 0.0
+    u[:, -1] = float(np.nextafter(np.float32(1.0), np.float32(0.0)))
+  elif kind in ('knots', 'knots_down'):
+    idx = torch.randint(0, cdf.shape[1], (R, N), generator=g)
+    u = torch.gather(cdf, 1, idx).clamp(max=1.0)
+    if kind == 'knots_down':
+      u = torch.nextafter(u, torch.zeros_like(u))
+  else:
+    assert kind == 'rand', kind
+  return u.contiguous()
+
+
+def linspace01_restated(N, fused=True):
+  """csrc/dyn_geometry.hip:linspace01 restated in NumPy: n * step below N / 2, fma(-step, N - 1 - n, 1) from there on (the 24 x 10 bit
+  product and its difference from 1 are exact in float64, so the one rounding to fp32 is the fused operation's).  fused=False: the
+  product rounded to fp32 first -- the kernels' formula before the ramp was settled, and what a torch build without FMA kernels gives."""
+  f = np.float32
+  step = f(1.0) / f(N - 1)
+  n = np.arange(N)
+  lo = n.astype(f) * step
+  k = (N - 1 - n)
+  hi = (1.0 - np.float64(step) * k.astype(np.float64)).astype(f) if fused else f(1.0) - k.astype(f) * step
+  return torch.from_numpy(np.where(n < N // 2, lo, hi).astype(f))
+
+
+def kernel_cdf_restated(w):
+  """k_fine_samples' cdf recipe restated in NumPy: interior weights [R,M] (in sample_pdf's order) -> cdf [R,M+1].  1e-5 added in fp32, the
+  total summed sequentially in double and rounded once, every quotient rounded to fp32, a sequential double prefix sum rounded per knot."""
+  wj = (w.float() + 1e-5).numpy()
+  total = np.cumsum(wj.astype(np.float64), axis=1)[:, -1:].astype(np.float32)
+  pdf = (wj / total).astype(np.float32)
+  cdf = np.cumsum(pdf.astype(np.float64), axis=1).astype(np.float32)
+  return torch.from_numpy(np.concatenate([np.zeros_like(cdf[:, :1]), cdf], axis=1))
+
+
+COMPOSITE_SHAPES = [(1, 2), (3, 63), (4, 64), (5, 65), (9, 128), (6, 129), (5, 200), (3, 256), (1030, 64)]  # (R, S)
+COMPOSITE_MODIFIERS = ('plain', 'opaque', 'masked', 'chunk_edge', 'count_head', 'count_tail')
+
+
+def composite_case(R, S, seed=0, modifier='plain'):
+  """raw_dy, raw_st [R,S,4], z [R,S] sorted, pm_dy, pm_st [R,S] bool for k_composite.  Modifiers: 'opaque' (every 7th dynamic logit 50, every 11th
+  static logit 1e4), 'masked' (every logit -1e9), 'chunk_edge' (a logit of 40 at samples 63, 64, 127, 128 -- either side of the kernel's 64-sample
+  chunks -- of every second ray), 'count_head' / 'count_tail' (exactly 7, 8 or 9 observed samples per ray and branch, every pair of counts
+  within nine rays, at the start / at the end of the ray; the ray mask is `count > 8`)."""
+  g = _gen(seed, R, S, 4)
+  raw_dy = torch.randn(R, S, 4, generator=g) * torch.tensor([1, 1, 1, 3.0])
+  raw_st = torch.randn(R, S, 4, generator=g) * torch.tensor([1, 1, 1, 3.0])
+  z = torch.sort(torch.rand(R, S, generator=g) * 10 + 0.5, dim=1)[0]
+  pm_dy = torch.rand(R, S, generator=g) > 0.7
+  pm_st = torch.rand(R, S, generator=g) > 0.9
+  if modifier == 'opaque':
+    raw_dy[:, ::7, 3] = 50.0
+    raw_st[:, 3::11, 3] = 1e4
+  elif modifier == 'masked':
+    raw_dy[..., 3] = -1e9
+    raw_st[..., 3] = -1e9
+  elif modifier == 'chunk_edge':
+    for s in (63, 64, 127, 128):
+      if s < S:
+        raw_dy[0::2, s, 3] = 40.0
+        raw_st[1::4, s, 3] = 40.0
+  elif modifier in ('count_head', 'count_tail'):
+    pm_dy[:] = False
+    pm_st[:] = False
+    for r in range(R):
+      n, m = min(7 + (r + 1) % 3, S), min(7 + ((r + 1) // 3) % 3, S)  # ray 0: (8, 7), ray 1: (9, 7), ray 2: (7, 8), ray 3: (8, 8), ...
+      if modifier == 'count_head':
+        pm_dy[r, :n] = True
+        pm_st[r, :m] = True
+      else:
+        pm_dy[r, S - n:] = True
+        pm_st[r, S - m:] = True
+  else:
+    assert modifier == 'plain', modifier
+  return raw_dy, raw_st, z, pm_dy, pm_st

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import cases
 import parity
 
 pytestmark = pytest.mark.emu
@@ -50,3 +51,33 @@ def test_trajectory_points_fused_into_gather_and_flows(emu):
 
 def test_expected_scene_flow(emu):
   parity.check_expected_scene_flow(emu)
+
+
+# ---- the per-ray kernels at their edges (small twins of tests/test_gpu_parity.py's entries) -----------------------------------------------
+def test_sampling_edges(emu):
+  parity.check_sampling_edges(emu, S=2)
+  for R, S in ((3, 85), (4, 64), (1, 257)):  # R * S = 255, 256, 257: one element short of, exactly and one past a 256-thread workgroup
+    parity.check_sampling_edges(emu, S=S, R=R)
+
+
+def test_composite_edges(emu):
+  parity.check_composite_edges(emu, shapes=[s for s in cases.COMPOSITE_SHAPES if s[0] < 100])
+
+
+@pytest.mark.parametrize('R,S,N', cases.FINE_SAMPLE_SHAPES)
+def test_fine_samples_edges(emu, R, S, N):
+  r = parity.check_fine_samples_edges(emu, R, S, N, with_sample_pdf=(R, S, N) in cases.FINE_SAMPLE_PDF_SHAPES)
+  print('  knot ties:', {k.split(' [')[0] + k[-7:-1]: v['knot_ties'] for k, v in r.items() if v['mismatches']}, ' largest excluded share:', max(v['excluded'] for v in r.values()))
+
+
+@pytest.mark.parametrize('S,N', cases.RAMP_DETECTOR_SHAPES)
+def test_ramp_detector(emu, S, N):
+  parity.check_ramp_detector(emu, S, N)
+
+
+def test_ramp_bits(emu):
+  parity.check_ramp_bits(emu)
+
+
+def test_project_gather_row_order_fallback(emu):
+  parity.check_project_gather_row_order(emu)

@@ -285,6 +285,321 @@ def check_fine_samples(device, golden, S=64):
   return total_mismatch
 
 
+def check_composite_case(device, R, S, seed=0, modifier='plain', two=True):
+  """k_composite on one cases.composite_case: the reference's tolerances of check_composite (2e-6 + 1e-5 |ref|, ray mask exact) against the fp32
+  oracle, AND float64 as the arbiter (the kernel within twice the fp32 oracle's own distance from the float64 values, plus the same floor) --
+  the two-branch form with and without the per-sample outputs, the one-branch form likewise; entries a form does not produce must be None."""
+  raw_dy, raw_st, z, pm_dy, pm_st = cases.composite_case(R, S, seed, modifier)
+  tag = f'[{modifier} R={R} S={S}]'
+
+  def held(out, ref, ref64, keys, what):
+    for k in keys:
+      assert_close(out[k], ref[k], 2e-6, 1e-5, f'{what} {k}')
+      err64, own64 = (cpu(out[k]).double() - ref64[k]).abs(), (ref[k].double() - ref64[k]).abs()
+      lim = 2.0 * own64 + 2e-6 + 1e-5 * ref64[k].abs()
+      record_margin(f'{what} {k} vs float64 (limit: twice the fp32 oracle\'s own error + floor)', err64, lim)
+      assert bool((err64 <= lim).all()), f'{what} {k} {tag}: {float(err64.max()):.3e} from float64 where the fp32 oracle is {float(own64.max()):.3e}'
+    assert_bitexact(out['mask'] > 0, ref['mask'], f'{what} mask {tag}')
+    assert bool(((cpu(out['mask']) == 0) | (cpu(out['mask']) == 1)).all())
+
+  d = lambda x: x.to(device)
+  if two:
+    ref = O.raw2outputs(raw_dy, raw_st, z, pm_dy, pm_st)
+    ref64 = O.raw2outputs(raw_dy.double(), raw_st.double(), z.double(), pm_dy, pm_st)
+    out = ops.composite(d(raw_dy), d(z), d(pm_dy.float()), d(raw_st), d(pm_st.float()))
+    held(out, ref, ref64, ('rgb', 'rgb_static', 'rgb_dy', 'depth', 'alpha_dy', 'weights_dy', 'weights_st', 'alpha', 'weights'), 'raw2outputs')
+    lean = ops.composite(d(raw_dy), d(z), d(pm_dy.float()), d(raw_st), d(pm_st.float()), per_sample=False)
+    held(lean, ref, ref64, ('rgb', 'rgb_static', 'rgb_dy', 'depth', 'weights'), 'raw2outputs per_sample=False')
+    for k in ('alpha', 'alpha_dy', 'weights_dy', 'weights_st'):
+      assert lean[k] is None, f'per_sample=False returned {k}'
+    for k in ('rgb', 'rgb_static', 'rgb_dy', 'depth', 'weights', 'mask'):
+      assert_bitexact(lean[k], out[k], f'per_sample=False changes {k} {tag}')
+  ref = O.raw2outputs_vanilla(raw_dy, z, pm_dy)
+  ref64 = O.raw2outputs_vanilla(raw_dy.double(), z.double(), pm_dy)
+  out = ops.composite(d(raw_dy), d(z), d(pm_dy.float()))
+  held(out, ref, ref64, ('rgb', 'depth', 'alpha', 'weights'), 'raw2outputs_vanilla')
+  lean = ops.composite(d(raw_dy), d(z), d(pm_dy.float()), per_sample=False)
+  held(lean, ref, ref64, ('rgb', 'depth', 'weights'), 'raw2outputs_vanilla per_sample=False')
+  assert lean['alpha'] is None
+  for o_ in (out, lean):
+    for k in ('rgb_static', 'rgb_dy', 'alpha_dy', 'weights_dy', 'weights_st'):
+      assert o_[k] is None, f'the one-branch form returned {k}'
+  for k in ('rgb', 'depth', 'weights', 'mask'):
+    assert_bitexact(lean[k], out[k], f'vanilla per_sample=False changes {k} {tag}')
+
+
+def check_composite_edges(device, shapes=None):
+  """every modifier of cases.COMPOSITE_MODIFIERS on every shape (S = 1: the one-branch form on random logits only -- the reference's two-branch
+  form is not called with one sample)"""
+  for R, S in (shapes if shapes is not None else cases.COMPOSITE_SHAPES):
+    for i, mod in enumerate(cases.COMPOSITE_MODIFIERS):
+      check_composite_case(device, R, S, seed=i, modifier=mod)
+  check_composite_case(device, 3, 1, seed=9, two=False)
+  check_composite_case(device, 1030, 1, seed=10, two=False)
+
+
+FINE_SAMPLE_CAPS = {'onehot1': 0.25, 'knots': 0.25, 'knots_down': 0.25}  # share of samples the value check may exclude (default 0.02)
+
+
+def _pdf_domain(z, w, inv_uniform):
+  """bins [R,S-1], interior weights [R,S-2] in the order sample_pdf sees them (render_ray.py:790-821)"""
+  if inv_uniform:
+    inv_z = 1.0 / z
+    return torch.flip(0.5 * (inv_z[:, 1:] + inv_z[:, :-1]), dims=[1]).contiguous(), torch.flip(w[:, 1:-1], dims=[1]).contiguous()
+  return (0.5 * (z[:, 1:] + z[:, :-1])).contiguous(), w[:, 1:-1].contiguous()
+
+
+def _index_report(case, samples, mismatches, knot_ties, bound):
+  """one CHAIN_INDEX_REPORT row per case family, accumulated over the shapes a session runs"""
+  row = next((c for c in CHAIN_INDEX_REPORT if c['case'] == case), None)
+  if row is None:
+    row = dict(case=case, samples=0, mismatches=0, knot_ties=0, tie_bound=0.0)
+    CHAIN_INDEX_REPORT.append(row)
+  row['samples'] += samples
+  row['mismatches'] += mismatches
+  row['knot_ties'] += knot_ties
+  row['tie_bound'] = max(row['tie_bound'], bound)
+
+
+def check_fine_samples_case(device, z, w, N, inv_uniform, u=None, what='', cap=0.02, ties_allowed=True):
+  """k_fine_samples on given coarse depths z [R,S] and weights w [R,S] (u [R,N] or None: the deterministic ramp), the protocol of
+  check_fine_samples without a golden.
+
+  Indices against the fp32 oracle's above_inds.  A difference is legitimate only as a knot tie, by check_render_rays_mv's rule: every oracle knot
+  the index jumped lies within `bound` of u.  `bound` is measured on the oracle alone: the largest |cdf32 - cdf64| of the case (pdf_to_cdf on the
+  float64 copy of the same weights) plus one ulp of u.  (The kernel's knots differ from torch's in the last bit -- its normaliser is the correctly
+  rounded sum, torch.sum's bits depend on the CPU's vector width --, so bit-equality at a knot is not a property either side has.)
+  ties_allowed=False (the ramp detector): no allowance at all.
+
+  Values: float64 arbitrates (O.sample_pdf on .double() inputs, the same fp32 u).  Per sample the kernel may be max(tol, 2 x the fp32 oracle's own
+  distance from float64) from it, tol = cdf_sample_conditioning's bound + check_fine_samples' rounding floor (2e-6 |ref| + 1e-7).  A sample at a
+  legitimate knot tie may instead be within the tol of the bin on the kernel's side of the knot of the float64 value at the kernel's own index
+  (beside a bin of mass below 1e-5 the reference itself moves by a bin width across the knot).  Not held: samples cdf_sample_conditioning marks
+  `tie` (bin mass within 4e-7 of the hard 1e-5 threshold; at a knot tie also the kernel-side bin's).  Their share is capped by `cap`, a condition
+  of the test (the oracle alone stays
+  inside it), not a measurement.  The sorted union is bit-exact against a sort of the kernel's own depths."""
+  det = u is None
+  R, S = z.shape
+  z_all_r, inds_r = O.fine_z_vals(z, w, N, inv_uniform, det, u, return_inds=True)
+  z_all, z_s, inds = ops.fine_samples(z.to(device), w.to(device), N, inv_uniform, None if det else u.to(device), want_inds=True)
+  z_all, z_s, got_i = cpu(z_all), cpu(z_s), cpu(inds).long()
+  assert bool(torch.isfinite(z_all).all()) and bool(torch.isfinite(z_all_r).all()), f'{what}: non-finite depths'
+  bins, ww = _pdf_domain(z, w, inv_uniform)
+  M = ww.shape[1]
+  uu = torch.linspace(0.0, 1.0, N).unsqueeze(0).repeat(R, 1) if det else u
+  cdf = O.pdf_to_cdf(ww)
+  cdf64 = O.pdf_to_cdf(ww.double())
+  assert bool((got_i >= 0).all()) and bool((got_i <= M).all()), f'{what}: index out of range'
+  # ---- indices
+  # against the kernel's own recipe first, with no allowance: the cdf restated in NumPy (cases.kernel_cdf_restated: IEEE fp32 / fp64 operations in a
+  # fixed order, so the device has no freedom in its bits) and counted through like the reference counts -- a wrong comparison, probe or LDS slot
+  # shows here even where the oracle's knots would excuse it as a tie
+  inds_own = O.invert_cdf(bins, cases.kernel_cdf_restated(ww), uu)[1]
+  assert torch.equal(got_i, inds_own), (f'{what}: {int((got_i != inds_own).sum())} of {got_i.numel()} indices differ from the count over the kernel\'s own cdf recipe '
+                                        f'(first at {torch.nonzero(got_i != inds_own)[0].tolist()})')
+  mism = got_i != inds_r
+  n_mis = int(mism.sum())
+  ulp_u = (torch.nextafter(uu, torch.full_like(uu, 2.0)) - uu).double()
+  bound = float((cdf.double() - cdf64).abs().max())
+  lo, hi = torch.minimum(got_i, inds_r), torch.maximum(got_i, inds_r)
+  span = int((hi - lo).max())
+  far = torch.zeros_like(uu, dtype=torch.float64)       # largest distance from u of an oracle knot the index jumped
+  light = torch.zeros_like(mism)                         # a bin beside a jumped knot has mass below the reference's 1e-5 threshold
+  for k in range(-1, span):
+    j = lo + k
+    ok = mism & (j >= 0) & (j < hi)
+    jc = j.clamp(0, M - 1)
+    light |= ok & ((torch.gather(cdf, 1, jc + 1) - torch.gather(cdf, 1, jc)) < 1e-5)
+    if k >= 0:
+      far = torch.where(ok, torch.maximum(far, (torch.gather(cdf, 1, jc).double() - uu.double()).abs()), far)
+  unexplained = mism & (far > bound + ulp_u)
+  n_un = int(unexplained.sum())
+  _index_report(f'k_fine_samples {what.split(" ")[0]}', int(mism.numel()), n_mis, n_mis - n_un, bound + float(ulp_u.max()))
+  if not ties_allowed:
+    assert n_mis == 0, f'{what}: {n_mis} of {mism.numel()} indices differ from the oracle\'s where the two cdfs are the same bits (first at {torch.nonzero(mism)[0].tolist()})'
+  assert n_un == 0, (f'{what}: {n_un} inverse-CDF index flips that are not knot ties (of {n_mis} flips, {mism.numel()} samples; bound {bound:.2e}, '
+                     f'worst knot distance {float(far[unexplained].max()):.2e})')
+  # ---- values, in sample_pdf's domain (1/z when inv_uniform)
+  ref32 = O.sample_pdf(bins, ww.clone(), N, det=False, u=uu)
+  ref64 = O.sample_pdf(bins.double(), ww.double(), N, det=False, u=uu)
+  tie, tol = O.cdf_sample_conditioning(z, w, N, inv_uniform, det, u)
+  got = 1.0 / z_s.double() if inv_uniform else z_s.double()
+  own = (ref32.double() - ref64).abs()
+  lim = torch.maximum(tol.double() + 2e-6 * ref64.abs() + 1e-7, 2.0 * own)
+  # A legitimate knot tie is evaluated in ANOTHER bin than the oracle's: in the bin on the kernel's side of the knot.  Across a knot beside a bin of
+  # mass below 1e-5 the reference itself lands a bin width away (t = (u - c) / 1 there), and beside a bin of small mass m the applicable conditioning
+  # is that bin's (width 4e-7 / m), not the oracle bin's.  So such a sample may instead be within that bin's own tol of the float64 value AT THE
+  # KERNEL'S INDEX (stricter than leaving it out); it is excluded only if that bin's mass is itself within the threshold band.
+  a_i, b_i = got_i, (got_i - 1).clamp(min=0)
+  c_hi, c_lo = torch.gather(cdf64, 1, a_i), torch.gather(cdf64, 1, b_i)
+  b_hi, b_lo = torch.gather(bins.double(), 1, a_i), torch.gather(bins.double(), 1, b_i)
+  mass_k = torch.gather(cdf, 1, a_i) - torch.gather(cdf, 1, b_i)
+  den = c_hi - c_lo
+  alt64 = b_lo + (uu.double() - c_lo) / torch.where(mass_k.double() < 1e-5, torch.ones_like(den), den) * (b_hi - b_lo)
+  tol_k = (b_hi - b_lo).abs() * 4e-7 / torch.where(mass_k < 1e-5, torch.ones_like(mass_k), mass_k).double()
+  excluded = tie | (mism & ((mass_k - 1e-5).abs() < 4e-7))
+  share = float(excluded.float().mean())
+  used = (got - ref64).abs() / lim
+  used = torch.where(mism, torch.minimum(used, (got - alt64).abs() / (tol_k + 2e-6 * alt64.abs() + 1e-7)), used)
+  record_margin(f'k_fine_samples {what.split(" ")[0]} vs float64', used[~excluded], torch.ones_like(used[~excluded]))
+  over = (used > 1.0) & ~excluded
+  assert int(over.sum()) == 0, (f'{what}: {int(over.sum())} samples further from float64 than max(tol, twice the fp32 oracle), worst {float(used[over].max()):.2f} '
+                                f'of the limit at {torch.nonzero(over)[0].tolist()} ({int((over & mism).sum())} of them at knot ties)')
+  # (with N < 4 one sample of a ray is already more than a quarter of it -- one-hot 1.0 at N = 3 has exactly one threshold sample of three by
+  # construction --, so there the cap is held on the pooled samples of the kind at that shape, by check_fine_samples_edges)
+  assert share <= cap or N < 4, f'{what}: {share:.3f} of the samples excluded from the value check (cap {cap})'
+  # ---- the merge is pure data movement: bit-exact against a sort of the kernel's own new depths
+  assert_bitexact(z_all, torch.sort(torch.cat([z, z_s], dim=1), dim=1)[0], f'{what} sorted union')
+  assert bool((z_all[:, 1:] >= z_all[:, :-1]).all()), f'{what}: fine depths not sorted'
+  return dict(mismatches=n_mis, knot_ties=n_mis - n_un, excluded=share, n_excluded=int(excluded.sum()), samples=int(excluded.numel()), bound=bound)
+
+
+def check_sample_pdf_case(device, z, w, N, inv_uniform, u=None, what=''):
+  """render_ray.sample_pdf (k_sample_pdf, the helper export) on the same case: its samples are k_fine_samples' own -- bit for bit in depth, and
+  through one correctly rounded reciprocal in disparity --, so check_fine_samples_case's protocol carries over; and it adds 1e-5 to its
+  weights argument in place, like the reference (render_ray.py:23).  (The export draws its own u when det=False: a given u goes through the ABI.)"""
+  from dynibar_amd import render_ray
+  bins, ww = _pdf_domain(z, w, inv_uniform)
+  R, M = ww.shape
+  wd, bd = ww.clone().to(device).contiguous(), bins.to(device).contiguous()
+  if u is None:
+    smp = render_ray.sample_pdf(bd, wd, N, det=True)
+  else:
+    ud = u.to(device).contiguous()
+    smp = torch.empty((R, N), dtype=torch.float32, device=device)
+    ops.call('dyn_sample_pdf', ops.ptr(bd), ops.ptr(wd), ops.ptr(ud), R, M, int(N), ops.ptr(smp), ops.stream_of(smp))
+  assert_bitexact(wd, ww + 1e-5, f'{what} sample_pdf: the in-place + 1e-5 on its weights')
+  _, z_s, _ = ops.fine_samples(z.to(device), w.to(device), N, inv_uniform, None if u is None else u.to(device))
+  assert_bitexact(1.0 / cpu(smp) if inv_uniform else smp, z_s, f'{what} sample_pdf vs k_fine_samples')
+
+
+def fine_sample_inputs(kind, R, S, N, inv_uniform, mode):
+  """(z, w, u) of one case: kind in cases.FINE_WEIGHT_KINDS (mode 'det' | 'rand') or cases.FINE_U_KINDS (u built for the case)"""
+  z = cases.fine_sample_depths(R, S, inv_uniform)
+  if kind == 'dup_depth' and S > 3:  # one duplicated coarse depth: a bin of width zero beside it
+    z = z.clone()
+    z[:, S // 2] = z[:, S // 2 - 1]
+  w = cases.fine_sample_weights(kind, R, S)
+  if kind in cases.FINE_U_KINDS:
+    cdf = O.pdf_to_cdf(_pdf_domain(z, w, inv_uniform)[1]) if kind != 'u01' else None
+    return z, w, cases.fine_sample_u(kind, R, N, cdf)
+  return z, w, (None if mode == 'det' else cases.fine_sample_u('rand', R, N))
+
+
+def fine_sample_case_list():
+  return [(k, m) for k in cases.FINE_WEIGHT_KINDS for m in ('det', 'rand')] + [(k, 'given') for k in cases.FINE_U_KINDS]
+
+
+def check_fine_samples_edges(device, R, S, N, with_sample_pdf=False):
+  """every case of fine_sample_case_list() at one shape, both inv_uniform values"""
+  out = {}
+  for inv in (True, False):
+    for kind, mode in fine_sample_case_list():
+      z, w, u = fine_sample_inputs(kind, R, S, N, inv, mode)
+      what = f'{kind} {mode} [R={R} S={S} N={N} inv={int(inv)}]'
+      out[what] = check_fine_samples_case(device, z, w, N, inv, u, what, cap=FINE_SAMPLE_CAPS.get(kind, 0.02))
+      if with_sample_pdf:
+        check_sample_pdf_case(device, z, w, N, inv, u, what)
+  for kind in cases.FINE_WEIGHT_KINDS + cases.FINE_U_KINDS:
+    rows = [v for k, v in out.items() if k.split(' ')[0] == kind]
+    share = sum(v['n_excluded'] for v in rows) / float(sum(v['samples'] for v in rows))
+    assert share <= FINE_SAMPLE_CAPS.get(kind, 0.02), f'{kind} [R={R} S={S} N={N}]: {share:.3f} of the samples excluded from the value check'
+  return out
+
+
+def check_ramp_detector(device, S, N, R=3):
+  """All-zero weights, det=True, S - 2 = 2 (N - 1): the cdf is j / M and every second knot is a value of the u ramp, so one wrong last bit of a
+  ramp value moves an index.  The kernel's cdf recipe gives the oracle's cdf bit for bit here (asserted, on the oracle, with the recipe restated
+  in NumPy), so the indices must equal the oracle's with NO tie allowance: a flip can only come from u."""
+  assert S - 2 == 2 * (N - 1)
+  for inv in (True, False):
+    z = cases.fine_sample_depths(R, S, inv)
+    w = torch.zeros(R, S)
+    ww = _pdf_domain(z, w, inv)[1]
+    assert torch.equal(cases.kernel_cdf_restated(ww), O.pdf_to_cdf(ww)), 'precondition: the kernel\'s cdf recipe and torch\'s give the same bits on uniform weights'
+    assert torch.equal(cases.linspace01_restated(N), torch.linspace(0.0, 1.0, N)), 'precondition: the kernels\' ramp, restated, is torch.linspace'
+    on_knot = int((torch.linspace(0.0, 1.0, N)[None, :, None] == O.pdf_to_cdf(ww)[0][None, None, :]).any(-1).sum())
+    assert on_knot >= N // 2, f'the case does not put the ramp on knots ({on_knot} of {N})'
+    check_fine_samples_case(device, z, w, N, inv, None, f'ramp detector [S={S} N={N} inv={int(inv)}]', ties_allowed=False)
+
+
+def check_ramp_bits(device, Ns=range(2, 513)):
+  """the deterministic ramp itself, read out of k_sample_pdf: one bin [0, 1] of mass 1 maps u to itself (cdf = [0, 1], t = u / 1, 0 + t * 1), so
+  sample_pdf(det=True) returns u_n -- held bit for bit to torch.linspace(0, 1, N) for every N"""
+  from dynibar_amd import render_ray
+  bins = torch.tensor([[0.0, 1.0]], device=device)
+  bad = []
+  for N in Ns:
+    got = cpu(render_ray.sample_pdf(bins, torch.ones(1, 1, device=device), N, det=True))[0]
+    if not torch.equal(got, torch.linspace(0.0, 1.0, N)):
+      bad.append(N)
+  assert not bad, f'the kernels\' u ramp is not torch.linspace for N = {bad[:20]} ({len(bad)} values of N)'
+
+
+def check_sampling_edges(device, S, R=None, name='small'):
+  """k_sample_along_ray / k_points_from_z bit-exact at a given ray count (rays of the scene repeated with seeded jitter) and sample count: both
+  inv_uniform values, det and stratified, and points_from_z with and without a depth range"""
+  scene, o, d, uv, _ = cases.scene_case(name)
+  dr = scene['depth_range']
+  if R is not None:
+    g = torch.Generator().manual_seed(R)
+    idx = torch.arange(R) % o.shape[0]
+    o = (o[idx] + 0.05 * torch.randn(R, 3, generator=g)).contiguous()
+    d = (d[idx] + 0.05 * torch.randn(R, 3, generator=g)).contiguous()
+  R = o.shape[0]
+  t_rand = torch.rand(R, S, generator=torch.Generator().manual_seed(3))
+  for inv in (True, False):
+    for tr in (None, t_rand):
+      pts_r, z_r, s_r = O.sample_along_camera_ray(o, d, dr, S, inv, tr is None, tr)
+      pts, z, s = ops.sample_along_ray(o.to(device), d.to(device), dr.to(device), S, inv, None if tr is None else tr.to(device))
+      what = f'[R={R} S={S} inv={inv} det={tr is None}]'
+      assert_bitexact(z, z_r, f'z_vals {what}')
+      assert_bitexact(pts, pts_r, f'pts {what}')
+      assert_bitexact(s, s_r, f's_vals {what}')
+      pts2, s2 = ops.points_from_z(o.to(device), d.to(device), z_r.to(device), dr.to(device))
+      assert_bitexact(pts2, pts_r, f'points_from_z pts {what}')
+      assert_bitexact(s2, s_r, f'points_from_z s_vals {what}')
+      pts3, s3 = ops.points_from_z(o.to(device), d.to(device), z_r.to(device))
+      assert s3 is None
+      assert_bitexact(pts3, pts_r, f'points_from_z(depth_range=None) pts {what}')
+
+
+def _launch_counts():
+  """kernel name -> launches since the last read (csrc dyn_profile_*; reading resets)"""
+  import ctypes
+  from dynibar_amd import _lib
+  L = _lib.lib()
+  nk = L.dyn_profile_count()
+  ms, cnt = (ctypes.c_float * nk)(), (ctypes.c_int * nk)()
+  L.dyn_profile_read(ms, cnt)
+  L.dyn_profile_name.restype = ctypes.c_char_p
+  return {L.dyn_profile_name(i).decode(): cnt[i] for i in range(nk) if cnt[i]}
+
+
+def check_project_gather_row_order(device, name='wide24', S=24):
+  """k_project_gather, the row-order form dyn_project_gather falls back to when 64 % (F / 4) != 0 (here F = 24 feature maps: six float4 lanes per row,
+  ten rows per pass, four idle lanes): bit-exact against the oracle from the reference's own matrices with zero mask flips, like the tile form; the
+  per-sample mask of its second launch (dyn_sample_mask) at both thresholds; the fused trajectory form against the materialised one.  That the
+  fallback ran is read off the launch profile: only it launches k_sample_mask from within dyn_project_gather."""
+  from dynibar_amd import _lib
+  scene = cases.scene_case(name)[0]
+  assert scene['featmaps'].shape[1] == 24 and 64 % (24 // 4) != 0
+  flips, worst = check_project_gather_same_matrix(device, name, S=S)
+  assert flips == 0, f'{flips} mask flips'
+  L = _lib.lib()
+  L.dyn_profile_enable(1)
+  try:
+    _launch_counts()
+    check_project_gather(device, name, S=S)  # (its own sample_mask call + the two by-product masks of the fallback)
+    c = _launch_counts()
+    assert c.get('k_project_gather', 0) == 4 and c.get('k_sample_mask', 0) == 3, f'the row-order fallback was not taken: {c}'
+    check_fused_trajectory(device, name, S=S)
+    c = _launch_counts()
+    assert c.get('k_project_gather', 0) == 3 and c.get('k_sample_mask', 0) == 3, f'the row-order fallback was not taken: {c}'
+  finally:
+    L.dyn_profile_enable(0)
+
+
 def _weights(which):
   return cases.model_weights_trained() if which == 'trained' else cases.model_weights(0)
 

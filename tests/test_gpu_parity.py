@@ -466,3 +466,41 @@ def test_train_gemm_random_shapes(dev):
 def test_training_with_recomputed_hidden_layers(dev):
   """DYNIBAR_TRAIN_RECOMPUTE=1 / train_static.RECOMPUTE_HIDDEN: memory for time, same numbers."""
   parity.check_train_recompute(dev)
+
+
+# ---- the per-ray kernels at their edges: resampling (K4), compositing (K2), sampling, the gather's row-order fallback ------------------------
+@pytest.mark.parametrize('R,S', [(None, 2), (3, 85), (4, 64), (1, 257), (4099, 64)])
+def test_sampling_edges(dev, R, S):
+  """two samples per ray; R * S one short of, exactly and one past a 256-thread workgroup; 4099 rays -- bit-exact, points_from_z with and without a depth range"""
+  parity.check_sampling_edges(dev, S=S, R=R)
+
+
+def test_composite_edges(dev):
+  """S = 1 ... 256 (either side of the 64-sample chunks), R = 1 ... 1030; opaque samples at the chunk edges (the carried transmittance), all-masked rays,
+  exactly 7 / 8 / 9 observed samples at the head and at the tail of a ray; per_sample=False and the one-branch form on every case; float64 arbitrates"""
+  parity.check_composite_edges(dev)
+
+
+@pytest.mark.parametrize('R,S,N', cases.FINE_SAMPLE_SHAPES + [cases.FINE_SAMPLE_SHAPE_LARGE])
+def test_fine_samples_edges(dev, R, S, N):
+  """k_fine_samples beyond one workgroup, at N != S, at both LDS splits and on degenerate rays and u values (tests/parity.py:check_fine_samples_case states
+  the protocol); the sample_pdf export on three of the shapes"""
+  r = parity.check_fine_samples_edges(dev, R, S, N, with_sample_pdf=(R, S, N) in cases.FINE_SAMPLE_PDF_SHAPES)
+  print(f'  [R={R} S={S} N={N}] knot ties:', {k.split(' [')[0] + k[-7:-1]: v['knot_ties'] for k, v in r.items() if v['mismatches']},
+        ' largest excluded share:', round(max(v['excluded'] for v in r.values()), 4), ' bound:', max(v['bound'] for v in r.values()))
+
+
+@pytest.mark.parametrize('S,N', cases.RAMP_DETECTOR_SHAPES)
+def test_ramp_detector(dev, S, N):
+  """uniform cdf whose every second knot is a ramp value: indices equal the oracle's with no tie allowance"""
+  parity.check_ramp_detector(dev, S, N)
+
+
+def test_ramp_bits(dev):
+  """the deterministic u ramp, read out through sample_pdf on one unit bin, is torch.linspace(0, 1, N) bit for bit for N = 2 ... 512"""
+  parity.check_ramp_bits(dev)
+
+
+def test_project_gather_row_order_fallback(dev):
+  """F = 24 feature maps: dyn_project_gather takes its row-order kernel and a second launch for the per-sample mask (read off the launch profile)"""
+  parity.check_project_gather_row_order(dev)
