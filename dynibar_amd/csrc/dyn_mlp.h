@@ -18,7 +18,8 @@
 //    k_net_points still multiplies with that instruction directly: mfma32 below.)
 // Three layer loops on the shipped engine (round 4): mlp_layer_b6 (two-slot ring, pair-granular pipeline: the kernels that run two or three waves per
 // SIMD -- k_static_views, k_dynamic_views, k_selftest), mlp_layer_b6_duo (three-slot ring with a mid-chunk barrier, two output tiles interleaved, A
-// fragments four pairs ahead: the kernels that run ONE wave per SIMD -- k_motion_mlp, k_net_points) and mlp_layer_b6_lds (weights resident in LDS,
+// fragments four pairs ahead: the kernels that run ONE wave per SIMD -- k_motion_mlp, k_net_points -- and, two pairs ahead with the accumulators in the architectural
+// registers, the two-wave point chain k_net_points_w8) and mlp_layer_b6_lds (weights resident in LDS,
 // no ring: k_static_blend, whose 104 KiB of weights fit).
 #pragma once
 #include <utility>
@@ -674,12 +675,8 @@ struct WeightRing3 {
   int waves;           // waves of the workgroup (compile-time at every call site)
   int cf;              // floats per chunk: (pairs per chunk) x B6_PAIR_FLOATS -- 48 KiB (24 pairs) by default, 32 KiB for the point kernels' stream
   int fill, issued;    // chunk being requested (-1: none) and how many of this wave's pieces of it have been issued
-  // Persistent workgroups walk the stream once per row tile ("pass"): chunk k of a pass sits in slot[k % 3], the slots rotate by `total` between passes,
-  // and the tail of a pass requests the first two chunks of the next one (wrap = 1, more = another pass follows: the only run-time value here).
-  float* slot[B6D_SLOTS];
+  float* slot[B6D_SLOTS];        // chunk k sits in slot[k % 3]
   unsigned lds_slot[B6D_SLOTS];  // lds_wave of each slot (SGPRs)
-  int wrap;
-  bool more;
 #ifdef DYN_PHASE_TIMING
   int kid;
 #endif
@@ -705,9 +702,8 @@ __device__ __forceinline__ int ring3_pieces(const WeightRing3& R) { return R.cf 
 __device__ __forceinline__ void ring3_piece(const WeightRing3& R, int chunk, int k) {
   const int per_wave = R.cf / R.waves;
   const int grp = k / 6, i = k % 6;
-  const int sc = chunk >= R.total ? chunk - R.total : chunk;  // chunks `total`, `total + 1` of a pass are chunks 0, 1 of the next one
-  const float* g = R.glane + (long)sc * R.cf + grp * 1536;
-  const float* gu = R.gbase + (long)sc * R.cf + grp * 1536;  // (uniform base; the lane's offset within the wave's slice is R.lane_off)
+  const float* g = R.glane + (long)chunk * R.cf + grp * 1536;
+  const float* gu = R.gbase + (long)chunk * R.cf + grp * 1536;  // (uniform base; the lane's offset within the wave's slice is R.lane_off)
   const unsigned l = R.lds_slot[chunk % B6D_SLOTS] + (unsigned)(grp * 1536 * sizeof(float));
   float* le = R.slot[chunk % B6D_SLOTS] + (threadIdx.x >> 6) * per_wave + 512 + grp * 1536;  // (emulator build)
   if (i == 0) ring3_dma<-2048>(g, le, l, gu, R.lane_off);
@@ -749,8 +745,6 @@ __device__ __forceinline__ void ring3_init(WeightRing3& R, const float* stream, 
   }
   R.fill = -1;
   R.issued = 0;
-  R.wrap = 0;
-  R.more = false;
   for (int j = 0; j < B6D_SLOTS; ++j) {
     R.slot[j] = lds + j * R.cf;
     R.lds_slot[j] = R.lds_wave + (unsigned)(j * R.cf * sizeof(float));
@@ -762,8 +756,7 @@ __device__ __forceinline__ void ring3_init(WeightRing3& R, const float* stream, 
 // first read of chunk R.next: chunk 0 is waited for here, every later chunk was published by the barrier in the middle of its predecessor
 __device__ __forceinline__ void ring3_enter(WeightRing3& R) {
   if (R.next != 0) return;
-  // chunk 1 (requested right behind chunk 0, at ring3_init or in the tail of the previous pass) may still be on its way: the barrier in the middle of
-  // chunk 0 waits for it
+  // chunk 1 (requested right behind chunk 0, at ring3_init) may still be on its way: the barrier in the middle of chunk 0 waits for it
   const int n = R.total > 1 ? ring3_pieces(R) : 0;
   if (n == 12) ring3_barrier<12>();
   else if (n == 8) ring3_barrier<8>();
@@ -782,7 +775,6 @@ __device__ __forceinline__ const float* ring3_slot(const WeightRing3& R, int chu
 #endif
 __device__ __forceinline__ void ring3_feed(WeightRing3& R, int half, int num, int den) {
   if (R.fill < 0) return;
-  if (R.fill >= R.total && !R.more) return;  // (the next pass's first chunks: only if there is a next pass)
   const int n = ring3_pieces(R), h0 = n / 2;
   int want = half == 0 ? (h0 * num + den - 1) / den : h0 + ((n - h0) * num + den - 1) / den;
   if (want > n) want = n;
@@ -792,26 +784,12 @@ __device__ __forceinline__ void ring3_feed(WeightRing3& R, int half, int num, in
 __device__ __forceinline__ void ring3_mid(WeightRing3& R) {
   DYN_PHASE_T0
   ring3_feed(R, 1, 1, 1);  // (whatever is left of chunk R.next + 1: normally nothing)
-  if (R.next + 1 < R.total || R.wrap) ring3_barrier();
+  if (R.next + 1 < R.total) ring3_barrier();
   DYN_PHASE_WAIT(R, R.next);
-  R.fill = (R.next + 2 < R.total || R.wrap) ? R.next + 2 : -1;
+  R.fill = R.next + 2 < R.total ? R.next + 2 : -1;
   R.issued = 0;
 }
-__device__ __forceinline__ void ring3_leave(WeightRing3& R) {
-  if (R.wrap && R.next == R.total - 1) ring3_feed(R, 1, 1, 1);  // the window of the next pass's chunk 1 ends with this pass
-  ++R.next;
-}
-// between two passes of a persistent workgroup: the next pass's chunks 0 and 1 have been requested into the slots this pass's chunks `total` and
-// `total + 1` would have taken; the pass starts like a fresh stream (ring3_enter waits for chunk 0 and publishes it)
-__device__ __forceinline__ void ring3_next_pass(WeightRing3& R) {
-  float* s0[B6D_SLOTS];
-  unsigned l0[B6D_SLOTS];
-  for (int j = 0; j < B6D_SLOTS; ++j) { s0[j] = R.slot[j]; l0[j] = R.lds_slot[j]; }
-  for (int j = 0; j < B6D_SLOTS; ++j) { R.slot[j] = s0[(R.total + j) % B6D_SLOTS]; R.lds_slot[j] = l0[(R.total + j) % B6D_SLOTS]; }
-  R.next = 0;
-  R.fill = -1;
-  R.issued = 0;
-}
+__device__ __forceinline__ void ring3_leave(WeightRing3& R) { ++R.next; }
 
 __device__ __forceinline__ float relu1(float v) {
 #if defined(__AMDGCN__)
@@ -845,18 +823,22 @@ __device__ __forceinline__ void dyn_static_for(F&& f) {
 // around it (hipcc moved the products of half a chunk behind the chunk's barrier and issued them as one block); two empty volatile asm
 // statements do: the first redefines the B operand (the MFMA cannot rise above it), the second redefines the result (it cannot sink below),
 // and volatile statements keep their order among themselves and against loads, stores, barriers and the scheduling barriers.
+// ACC_AGPR: the result is pinned in the accumulation registers (the one-wave-per-SIMD kernels: 256 + 256 registers) or in the architectural ones (a kernel
+// that runs two waves per SIMD has 256 in all, and a fixed share of accumulation registers would split them in two files for the whole kernel).
+template <bool ACC_AGPR = true>
 __device__ __forceinline__ f32x16 mfma_pinned(const u32x4v& a, u32x4v& b, f32x16 c) {
 #if defined(__AMDGCN__)
   asm volatile("" : "+v"(b));  // (the B operand: redefined in place, one chain per k-group -- touching the A fragment instead makes hipcc copy it for its second use)
   f32x16 d = mfma_bf16(a, b, c);
-  asm volatile("" : "+a"(d));
+  if constexpr (ACC_AGPR) asm volatile("" : "+a"(d));
+  else asm volatile("" : "+v"(d));
   return d;
 #else
   return mfma_bf16(a, b, c);
 #endif
 }
 
-template <int NT, int NSLOTS, int CP = B6_CHUNK_PAIRS, int AHEAD = B6D_AHEAD, class Feed>
+template <int NT, int NSLOTS, int CP = B6_CHUNK_PAIRS, int AHEAD = B6D_AHEAD, bool ACC_AGPR = true, class Feed>
 __device__ __forceinline__ void mlp_layer_b6_duo(WeightRing3& R, f32x16 (&acc)[NT], Feed&& feed) {
   constexpr int NG = (NSLOTS + 7) / 8;
   constexpr int NP = NG * NT;             // pairs of the layer
@@ -983,38 +965,38 @@ __device__ __forceinline__ void mlp_layer_b6_duo(WeightRing3& R, f32x16 (&acc)[N
     const B6A& a0 = q[P % QN];
     const B6A& a1 = q[(P + U - 1) % QN];
 #if DYN_SPLIT_TERMS == 6
-    acc[t0] = mfma_pinned(a0.lo, bh, acc[t0]);
-    if constexpr (U == 2) acc[t1] = mfma_pinned(a1.lo, bh, acc[t1]);
-    acc[t0] = mfma_pinned(a0.hi, bl, acc[t0]);
-    if constexpr (U == 2) acc[t1] = mfma_pinned(a1.hi, bl, acc[t1]);
-    acc[t0] = mfma_pinned(a0.mid, bm, acc[t0]);
-    if constexpr (U == 2) acc[t1] = mfma_pinned(a1.mid, bm, acc[t1]);
+    acc[t0] = mfma_pinned<ACC_AGPR>(a0.lo, bh, acc[t0]);
+    if constexpr (U == 2) acc[t1] = mfma_pinned<ACC_AGPR>(a1.lo, bh, acc[t1]);
+    acc[t0] = mfma_pinned<ACC_AGPR>(a0.hi, bl, acc[t0]);
+    if constexpr (U == 2) acc[t1] = mfma_pinned<ACC_AGPR>(a1.hi, bl, acc[t1]);
+    acc[t0] = mfma_pinned<ACC_AGPR>(a0.mid, bm, acc[t0]);
+    if constexpr (U == 2) acc[t1] = mfma_pinned<ACC_AGPR>(a1.mid, bm, acc[t1]);
 #endif
-    acc[t0] = mfma_pinned(a0.mid, bh, acc[t0]);
+    acc[t0] = mfma_pinned<ACC_AGPR>(a0.mid, bh, acc[t0]);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (U == 2) {
       // ---- gap 1
       if constexpr (P + AHEAD + 1 < NP) q[(P + AHEAD + 1) % QN] = load(P + AHEAD + 1);
       gap(std::integral_constant<int, 1>{});
-      acc[t1] = mfma_pinned(a1.mid, bh, acc[t1]);
+      acc[t1] = mfma_pinned<ACC_AGPR>(a1.mid, bh, acc[t1]);
       __builtin_amdgcn_sched_barrier(0);
       gap(std::integral_constant<int, 2>{});
     }
-    acc[t0] = mfma_pinned(a0.hi, bm, acc[t0]);
+    acc[t0] = mfma_pinned<ACC_AGPR>(a0.hi, bm, acc[t0]);
     if constexpr (U == 2) {
       __builtin_amdgcn_sched_barrier(0);
       gap(std::integral_constant<int, 3>{});
       dma(std::integral_constant<int, 1>{});
-      acc[t1] = mfma_pinned(a1.hi, bm, acc[t1]);
+      acc[t1] = mfma_pinned<ACC_AGPR>(a1.hi, bm, acc[t1]);
       __builtin_amdgcn_sched_barrier(0);
       gap(std::integral_constant<int, 4>{});
     }
-    acc[t0] = mfma_pinned(a0.hi, bh, acc[t0]);
+    acc[t0] = mfma_pinned<ACC_AGPR>(a0.hi, bh, acc[t0]);
     if constexpr (U == 2) {
       __builtin_amdgcn_sched_barrier(0);
       gap(std::integral_constant<int, 5>{});
       dma(std::integral_constant<int, U>{});
-      acc[t1] = mfma_pinned(a1.hi, bh, acc[t1]);
+      acc[t1] = mfma_pinned<ACC_AGPR>(a1.hi, bh, acc[t1]);
     } else {
       dma(std::integral_constant<int, U>{});
     }

@@ -90,6 +90,16 @@ SlotFn scaled(SlotFn fn, double scale) {
   return [=](int t, int i, int s, int h) -> float { return (float)((double)fn(t, i, s, h) * scale); };
 }
 
+// The three attention projections in the order k_net_points_w8 consumes them: per head t the two-tile layer (q_t, k_t), and in front of every even
+// head the two-tile layer (v_t, v_t+1).  (Output tile t of a projection is head t: d_k = 32.)
+void pack_qkv_by_head(std::vector<float>& out, const float* Wq, const float* Wk, const float* Wv) {
+  for (int hd = 0; hd < 4; ++hd) {
+    pack_net_layer(out, 2, 64, [=](int t, int i, int s, int h) -> float { return (t == 0 ? Wq : Wk)[(size_t)(32 * hd + i) * 128 + chain_feature(s, h)]; });
+    if (hd % 2 == 0)
+      pack_net_layer(out, 2, 64, [=](int t, int i, int s, int h) -> float { return Wv[(size_t)(32 * (hd + t) + i) * 128 + chain_feature(s, h)]; });
+  }
+}
+
 }  // namespace
 
 // ===================================================================================================================
@@ -118,14 +128,12 @@ enum {
 #define SA_L5_STEPS 64   /* vis_fc.0 / vis_fc.2 / vis_fc2.0 */
 constexpr int SA_CHUNKS = net_layer_chunks(8, SA_L1P_STEPS) + net_layer_chunks(8, SA_L1V_STEPS) + net_layer_chunks(2, SA_L2_STEPS) + net_layer_chunks(8, SA_L3P_STEPS) + net_layer_chunks(8, SA_L3V_STEPS) +
                           net_layer_chunks(4, SA_L4_STEPS) + 3 * net_layer_chunks(4, SA_L5_STEPS);
-// The point kernels (k_net_points) run one wave per SIMD on the interleaved layer loop with the three-slot ring (dyn_mlp.h, round 4).  Their LDS also
-// holds the ray attention's K / V images (32.5 KiB), so their weight streams are packed in chunks of PTS_CP = 16 pairs (32 KiB; 3 slots = 96 KiB,
-// what the two 48 KiB slots took).  DYN_POINTS_DUO = 0: the round-3 form (A/B builds; the 6-term bf16 build keeps it: its pairs are 3 KiB).
+// The point kernels run on the interleaved layer loop with the three-slot ring (dyn_mlp.h, round 4): k_net_points_w8 (rays of <= 128 samples) two waves per SIMD on
+// 256 rows per workgroup, k_net_points (longer rays) one wave per SIMD on 128.  Their LDS also holds the ray attention's K / V images (32.5 KiB), so their weight
+// streams are packed in chunks of PTS_CP = 16 pairs (32 KiB; 3 slots = 96 KiB, what the two 48 KiB slots took).  DYN_POINTS_DUO = 0: the round-3 form (A/B builds;
+// the 6-term bf16 build keeps it, on k_net_points for every ray length: its pairs are 3 KiB).
 #ifndef DYN_POINTS_DUO
 #define DYN_POINTS_DUO (DYN_SPLIT_TERMS == 3 ? 1 : 0)
-#endif
-#ifndef DYN_POINTS_PERSIST
-#define DYN_POINTS_PERSIST 0
 #endif
 #if DYN_POINTS_DUO
 #define PTS_CP 16
@@ -159,7 +167,11 @@ constexpr size_t ST_OFF_CTA = ST_OFF_C + (size_t)SC_CHUNKS * NET_CHUNK;
 constexpr size_t ST_OFF_CTB = ST_OFF_CTA + SA_CT;
 constexpr size_t ST_OFF_CTC = ST_OFF_CTB + SB_CT;
 constexpr size_t ST_OFF_REF = ST_OFF_CTC + SC_CT;  // ref_feature_fc.0: [35][66] then [35]
-constexpr size_t ST_BLOB_FLOATS = ST_OFF_REF + 35 * 66 + 36;
+// B8: the B stream once more with Q / K / V head by head, for the two-waves-per-SIMD point kernel (k_net_points_w8); the long-ray phases keep B.
+// Only the six Q / K / V chunks differ from B, but a weight ring walks ONE contiguous stream in consumption order, so the whole stream is there twice
+// (0.9 MB more in the static blob, 1.3 MB in the dynamic one).
+constexpr size_t ST_OFF_B8 = (ST_OFF_REF + 35 * 66 + 36 + 63) / 64 * 64;
+constexpr size_t ST_BLOB_FLOATS = ST_OFF_B8 + (DYN_POINTS_DUO ? (size_t)SB_CHUNKS * PTS_CHUNK : 0);
 
 // ===================================================================================================================
 // DynibarDynamic (mlp_network.py:129-316): layer programs and blob layout
@@ -185,7 +197,8 @@ constexpr size_t DY_OFF_CTA = DY_OFF_B + (size_t)DB_CHUNKS * PTS_CHUNK;
 constexpr size_t DY_OFF_CTB = DY_OFF_CTA + SA_CT;
 constexpr size_t DY_OFF_POSENC = DY_OFF_CTB + DB_CT;                 // [256 positions][2][64]
 constexpr size_t DY_OFF_TIME = DY_OFF_POSENC + 256 * 128;            // ray_dir_fc: W0 [256,21], b0 [256], W2 [35,256], b2 [35]
-constexpr size_t DY_BLOB_FLOATS = DY_OFF_TIME + 256 * 21 + 256 + 35 * 256 + 36;
+constexpr size_t DY_OFF_B8 = (DY_OFF_TIME + 256 * 21 + 256 + 35 * 256 + 36 + 63) / 64 * 64;  // as ST_OFF_B8
+constexpr size_t DY_BLOB_FLOATS = DY_OFF_B8 + (DYN_POINTS_DUO ? (size_t)DB_CHUNKS * PTS_CHUNK : 0);
 // channel (0..34, or -1) of the per-view feature held by register q of a lane of half h
 __host__ __device__ constexpr int da_c35(int q, int h) { return h == 0 ? q : (q < 17 ? 18 + q : -1); }
 
@@ -261,7 +274,8 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
   pack_net_layer(o, 4, SA_L5_STEPS, scaled(chained(T[ST_VIS2_W], nullptr, 128, 128, 128), DYN_ELU_POST));  // rows 0..127 = x_res
   pack_net_layer(o, 4, SA_L5_STEPS, scaled(chained(T[ST_VISB0_W], nullptr, 128, 128, 128), DYN_ELU_PRE));
   DYN_REQUIRE(o.size() == ST_OFF_B, "static pack: A stream size mismatch");
-  // ---- B ----
+  // ---- B (and B8: the same layers with Q / K / V head by head) ----
+  const auto pack_b = [&](bool by_head) {
 #if DYN_POINTS_DUO
   g_pack_chunk_pairs = PTS_CP;
 #endif
@@ -274,13 +288,19 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
     }, DYN_ELU_PRE));
   }
   pack_net_layer(o, 4, 129, scaled_wb(chained(T[ST_GEO2_W], T[ST_GEO2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0));
-  pack_net_layer(o, 4, 64, chained(T[ST_WQ], nullptr, 128, 128, 128));
-  pack_net_layer(o, 4, 64, chained(T[ST_WK], nullptr, 128, 128, 128));
-  pack_net_layer(o, 4, 64, chained(T[ST_WV], nullptr, 128, 128, 128));
+  if (by_head) {
+    pack_qkv_by_head(o, T[ST_WQ], T[ST_WK], T[ST_WV]);
+  } else {
+    pack_net_layer(o, 4, 64, chained(T[ST_WQ], nullptr, 128, 128, 128));
+    pack_net_layer(o, 4, 64, chained(T[ST_WK], nullptr, 128, 128, 128));
+    pack_net_layer(o, 4, 64, chained(T[ST_WV], nullptr, 128, 128, 128));
+  }
   pack_net_layer(o, 4, 64, chained(T[ST_FC], nullptr, 128, 128, 128));
   pack_net_layer(o, 4, 65, scaled(chained(T[ST_OG0_W], T[ST_OG0_B], 128, 128, 128), DYN_ELU_PRE));
   pack_net_layer(o, 4, 65, scaled(chained(T[ST_RGB0_W], T[ST_RGB0_B], 128, 128, 261), DYN_ELU_PRE));  // columns 0..127 = globalfeat part
   g_pack_chunk_pairs = B6_CHUNK_PAIRS;
+  };
+  pack_b(false);
   DYN_REQUIRE(o.size() == ST_OFF_C, "static pack: B stream size mismatch");
   // ---- C ----
   {
@@ -323,7 +343,11 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
   o.resize(ST_OFF_REF, 0.f);
   for (int i = 0; i < 35 * 66; ++i) o.push_back(T[ST_REFFEAT_W][i]);
   for (int i = 0; i < 35; ++i) o.push_back(T[ST_REFFEAT_B][i]);
-  o.resize(ST_BLOB_FLOATS, 0.f);
+  o.resize(ST_OFF_B8, 0.f);
+#if DYN_POINTS_DUO
+  pack_b(true);
+#endif
+  DYN_REQUIRE(o.size() == ST_BLOB_FLOATS, "static pack: B8 stream size mismatch");
   DYN_REQUIRE(!g_pack_range_error, "dyn_static_net_pack: a weight is outside the half-float range of the split engine (|w| >= 65504 or not finite)");
   for (size_t i = 0; i < ST_BLOB_FLOATS; ++i) blob[i] = o[i];
   return 0;
@@ -1412,24 +1436,6 @@ static int dyn_cu_count() {
   return n_cu[slot];
 }
 
-// grid of k_net_points<., 0>: one workgroup per row tile -- or, in the persistent build (-DDYN_POINTS_PERSIST=1), one per CU, each walking every n_cu-th tile
-static dim3 points_grid(dim3 full) {
-#if DYN_POINTS_DUO && DYN_POINTS_PERSIST
-  static int n_cu[DYN_MAX_DEVICES] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const int slot = (dev >= 0 && dev < DYN_MAX_DEVICES) ? dev : 0;
-  if (n_cu[slot] == 0) {
-    hipDeviceProp_t prop;
-    n_cu[slot] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  static const int no_persist = getenv("DYN_POINTS_NO_PERSIST") != nullptr;  // developer A/B: one workgroup per row tile, like the long-ray phases
-  return (no_persist || full.x <= (unsigned)n_cu[slot]) ? full : dim3((unsigned)n_cu[slot]);
-#else
-  return full;
-#endif
-}
-
 template <bool DYN, int PHASE>
 __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p) {
   constexpr int PHASE_KID = 1;
@@ -1455,31 +1461,7 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
 
   const int TPR = p.TPR;
   const float one_h0 = h == 0 ? 1.0f : 0.0f;
-  // -DDYN_POINTS_PERSIST=1 (measured in round 4, NOT the default): PHASE 0 as a persistent kernel -- one workgroup per CU walks row tiles blockIdx.x,
-  // + gridDim.x, ...; the tail of a pass pulls the next tile's geometry_fc inputs into the L2 (one dword per 16 bytes, summed into a value nobody
-  // reads; holding the 129 inputs themselves through the tail layers costs 80 spilled registers) and requests the next pass's first weight chunks.
-  // Motive: cycle stamps show a workgroup's first 15 k of ~104 k cycles going into its own start (132 KB of inputs at the rate a CU gets from HBM,
-  // the first weight chunks) with nothing else resident on the CU.  Result: k_net_points 487 us against 465-475 us with one workgroup per row tile,
-  // frame +2 ms: the prefetch doubles the L2 -> CU traffic of the inputs and the static tile assignment loses the dispatcher's balancing.
-  constexpr bool PERSIST = DYN_POINTS_PERSIST && DYN_POINTS_DUO && PHASE == 0;
-  const long n_wg = (p.n_tiles_b + 3) / 4;
-  // the geometry_fc inputs of row tile wgi: this lane's 33 float4 records
-  auto gin_src = [&](long wgi, bool& valid_) DYN_INLINE_LAMBDA {
-    const long tile_ = wgi * 4 + wave;
-    const long ray_ = tile_ / TPR;
-    valid_ = (ray_ < p.R) && ((int)(tile_ - ray_ * TPR) * 32 + j < p.S);
-    return reinterpret_cast<const float4*>(p.ws + p.o.off_gin) + (tile_ < p.n_tiles_b ? tile_ : 0) * SB_GIN_RECS * 64 + lane;
-  };
-#if DYN_POINTS_DUO
-  ring.wrap = PERSIST ? 1 : 0;
-#endif
-  long wgi = blockIdx.x;
-  do {  // (a loop only in the persistent form)
-  const bool more = PERSIST && wgi + gridDim.x < n_wg;
-#if DYN_POINTS_DUO
-  ring.more = more;
-#endif
-  const long tile = wgi * 4 + wave;
+  const long tile = (long)blockIdx.x * 4 + wave;
   const long ray = tile / TPR;
   const int kt_self = (int)(tile - ray * TPR);
   const int smp = kt_self * 32 + j;
@@ -1505,8 +1487,9 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
     f32x16 a9[8];
     {
       float gin[129];
-      bool gv;
-      const float4* src = gin_src(wgi, gv);
+      // the geometry_fc inputs of the row tile: this lane's 33 float4 records
+      const bool gv = valid;
+      const float4* src = reinterpret_cast<const float4*>(p.ws + p.o.off_gin) + (tile < p.n_tiles_b ? tile : 0) * SB_GIN_RECS * 64 + lane;
 #pragma unroll
       for (int i = 0; i < 32; ++i) {
         const float4 v = gv ? nt_load4<4>(src + i * 64) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1782,13 +1765,6 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
       for (int r = 0; r < 16; ++r) g[t][r] = (o[t][r] - mu) * rstd * gam[t * 16 + r] + bet[t * 16 + r];
   }
   DYN_PHASE(4);  // fc + LayerNorm done
-  float pf[SB_GIN_RECS];  // (persistent form) one dword of every 16 bytes of the next pass's geometry_fc inputs: pulled into the L2 ~14 k cycles ahead
-  if (PERSIST) {
-    bool gv;
-    const float* nsrc = reinterpret_cast<const float*>(gin_src(more ? wgi + gridDim.x : wgi, gv));
-#pragma unroll
-    for (int i = 0; i < SB_GIN_RECS; ++i) pf[i] = (more && gv) ? nsrc[i * 256] : 0.f;
-  }
   if (!DYN) {
     f32x16 a[4];
     acc_zero(a);
@@ -1859,25 +1835,351 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
     if (valid && h == 0) reinterpret_cast<float4*>(p.raw)[point] = make_float4(rgb[0], rgb[1], rgb[2], sigma);
   }
   DYN_PHASE(20);
-#if DYN_POINTS_DUO
-  if (PERSIST) {
-    // the prefetched dwords are summed HERE, behind everything the pass computes (the sum starts from a value the last stores produced, so hipcc cannot
-    // raise the additions -- and their wait for the loads -- into the tail layers)
-    float sink = nvalid;
-#if defined(__AMDGCN__)
-    asm volatile("" : "+v"(sink));
-#endif
-#pragma unroll
-    for (int i = 0; i < SB_GIN_RECS; ++i) sink += pf[i];
-#if defined(__AMDGCN__)
-    asm volatile("" ::"v"(sink));
-#endif
-    ring3_next_pass(ring);
-  }
-#endif
-  wgi += gridDim.x;
-  } while (PERSIST && wgi < n_wg);  // row tiles of this workgroup
 }
+
+#if DYN_POINTS_DUO
+// -------------------------------------------------------------------------------------------------------------------
+// The chain for rays of <= 128 samples: 8 waves (two per SIMD) and 256 rows per workgroup on ONE weight ring, so that every chunk streamed from the L2
+// serves 256 rows and a wave's waits (the start-up loads, the attention's LDS round trips, softmax, barriers) are covered by its SIMD partner.
+// Tile assignment as everywhere: tile = workgroup * 8 + wave, ray = tile / TPR; TPR is 1, 2 or 4, so a ray never straddles workgroups, and nothing a
+// ray computes depends on which wave or workgroup it sits in.  What keeps a lane within 256 registers:
+//  * geometry_fc.0 takes its 129 inputs in four K parts (32 + 32 + 32 + 33 slots: four calls of the layer loop on the same accumulators; the stream of the
+//    (8, 129) layer splits at chunk boundaries, so packing and summation order are those of the one-call form);
+//  * Q / K / V are evaluated head by head (output tile t of each projection is head t): the stream SB8 holds, per head, the pair (q_t, k_t) as one
+//    two-tile layer and, in front of every even head, (v_t, v_t+1); the head's attention runs before the next head's projections, so 48-64 registers
+//    of q, k, v are live instead of 192 -- and a layer's weight stream stands between the LDS phases of consecutive heads;
+//  * the K image and the V table of a head share one LDS region (K is dead once the scores exist): 3 x 32 KiB of ring + 33 KiB + tables;
+//  * (dynamic) ref_pts_fc.0 takes [globalfeat | PE(pts)] in two K parts as well.
+// The layer loop is mlp_layer_b6_duo with two pairs of A fragments ahead instead of four (the partner wave covers the LDS latency).
+// -------------------------------------------------------------------------------------------------------------------
+#define PTS8_LAYER(NT, NSLOTS) mlp_layer_b6_duo<NT, NSLOTS, PTS_CP, 2, false>
+#define SB8_VL_LD 260                   // V of one head: [32 features][256 points + pad]
+#define SB8_KV_FLOATS (32 * SB8_VL_LD)  // ... which also holds K of one head as [8 tiles][2 groups][hi | mid][64 lanes] x 16 bytes (8192 floats)
+static_assert(SB8_KV_FLOATS >= 8 * 2 * 2 * 64 * 4, "the K image fits the shared region");
+static_assert(pts_layer_chunks(8, 129) == 3 * pts_layer_chunks(8, 32) + pts_layer_chunks(8, 33) && 32 % (8 * (PTS_CP / 8)) == 0 && pts_layer_chunks(8, 81) == pts_layer_chunks(8, 64) + pts_layer_chunks(8, 17),
+              "the two-part layers split at a chunk boundary");
+static_assert(4 * pts_layer_chunks(2, 64) + 2 * pts_layer_chunks(2, 64) == 3 * pts_layer_chunks(4, 64), "the head-interleaved stream is as long as the plain one");
+
+// MAXT: the most key tiles a ray can have in this instance (2: rays of <= 64 samples, 4: <= 128) -- the score tiles of a head are 16 registers each
+template <bool DYN, int MAXT>
+__global__ void __launch_bounds__(DYN_VIEW_THREADS, 2) k_net_points_w8(StaticArgs p) {
+  constexpr int PHASE_KID = 1;
+  (void)PHASE_KID;
+  DYN_PHASE(0);
+  constexpr int CT = DYN ? DB_CT : SB_CT;
+  float* lds = reinterpret_cast<float*>(dyn_smem);
+  float* ctab = lds + PTS_RING_SLOTS * PTS_CHUNK;  // [SB_CT] / [DB_CT]
+  float* KV = ctab + CT;
+  const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5, wave = tid >> 6;
+  for (int i = tid; i < CT; i += DYN_VIEW_THREADS) ctab[i] = p.blob[(DYN ? DY_OFF_CTB : ST_OFF_CTB) + i];
+  PtsRing ring;
+  ring3_init(ring, p.blob + (DYN ? DY_OFF_B8 : ST_OFF_B8), DYN ? DB_CHUNKS : SB_CHUNKS, lds, DYN_VIEW_THREADS, PTS_CP);
+  DYN_PHASE_RING_KID(ring, 1);
+  lds_barrier();  // the constant table (the ring's own barrier waits for vmcnt only)
+
+  // Everything about the tile is wave-uniform and lives in scalar registers; what a lane needs of its point at the very end (its index) is worked out
+  // again there, and num_valid_obs is kept as the three conditions it decides: the chain has no registers to carry per-lane values through.
+  const int TPR = p.TPR;  // 1, 2 or 4 here, <= MAXT
+  const float one_h0 = h == 0 ? 1.0f : 0.0f;
+#if defined(__AMDGCN__)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+#else
+  const int wave_u = wave;
+#endif
+  const long tile = (long)blockIdx.x * (DYN_VIEW_THREADS / 64) + wave_u;
+  const int tpr_shift = TPR >> 1;  // log2(TPR)
+  const long ray = tile >> tpr_shift;
+  const int kt_self = (int)(tile & (TPR - 1));
+  const bool valid = (ray < p.R) && (kt_self * 32 + j < p.S);
+  bool q_ok, no_view, few_views;  // num_valid_obs > 1: the attention's query mask; == 0; < 1
+  {
+    const float nvalid = valid ? p.ws[p.o.off_nvalid + ray * p.S + kt_self * 32 + j] : 0.f;
+    q_ok = nvalid > 1.0f;
+    no_view = nvalid == 0.f;
+    few_views = nvalid < 1.0f;
+  }
+
+  f32x16 g[4];
+  {
+    f32x16 a9[8];
+    acc_zero(a9);
+    // the geometry_fc inputs of the row tile: this lane's 33 float4 records, [mean 16 | var 16 | (mean weight, 1)]
+    const float4* src = reinterpret_cast<const float4*>(p.ws + p.o.off_gin) + (tile < p.n_tiles_b ? tile : 0) * SB_GIN_RECS * 64 + lane;
+    // geometry_fc.0 in four K parts of 32, 32, 32 and 33 slots (8 records each, and the last record's .x)
+    dyn_static_for<3>([&](auto PART) DYN_INLINE_LAMBDA {  // (compile-time expansion: a loop the unroller gives up on would index registers at run time)
+      constexpr int part = decltype(PART)::value;
+      float gin[32];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float4 v = valid ? nt_load4<4>(src + (part * 8 + i) * 64) : make_float4(0.f, 0.f, 0.f, 0.f);
+        gin[i * 4] = v.x; gin[i * 4 + 1] = v.y; gin[i * 4 + 2] = v.z; gin[i * 4 + 3] = v.w;
+      }
+      PTS8_LAYER(8, 32)(ring, a9, [&](int s) { return gin[s]; });
+    });
+    {
+      float gin[33];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float4 v = valid ? nt_load4<4>(src + (24 + i) * 64) : make_float4(0.f, 0.f, 0.f, 0.f);
+        gin[i * 4] = v.x; gin[i * 4 + 1] = v.y; gin[i * 4 + 2] = v.z; gin[i * 4 + 3] = v.w;
+      }
+      gin[32] = valid ? src[32 * 64].x : (h == 1 ? 1.0f : 0.f);
+      PTS8_LAYER(8, 33)(ring, a9, [&](int s) { return gin[s]; });
+    }
+    acc_zero(g);
+    PTS8_LAYER(4, 129)(ring, g, [&](int s) { return s < 128 ? elu_s(a9[s / 16][s % 16]) : one_h0; });  // ELUs ride in the consumer's feed
+    acc_elu(g);
+  }
+  if (DYN) {
+    // globalfeat + pos_encoding (mlp_network.py:284): table rows in D-layout order [position][half][64]
+    const float4* pe = reinterpret_cast<const float4*>(p.blob + DY_OFF_POSENC + ((valid ? kt_self * 32 + j : 0) * 2 + h) * 64);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 v = pe[t * 4 + q];
+        g[t][q * 4] += v.x; g[t][q * 4 + 1] += v.y; g[t][q * 4 + 2] += v.z; g[t][q * 4 + 3] += v.w;
+      }
+  }
+  // ---- multi-head self-attention over the samples of the ray (mlp_network.py:13-31, 56-104), one head at a time ----
+  DYN_PHASE(1);  // geometry_fc done
+  f32x16 att[4];
+  {
+    const float inv_temp = 1.0f / 5.656854249492381f;  // d_k ** 0.5
+    const int wave0 = wave_u - kt_self;                 // first wave of this ray inside the workgroup
+    // The matmuls as in k_net_points: scores^T [key x query] = K . q^T with a key tile's K deposited in ITS lanes' register order as hi | mid half-float
+    // images; out^T [feature x query] = V^T . P with V^T rows read from the [feature][key] table and split on the fly.
+    auto split8 = [&](const float (&v)[8], u32x4v& hi, u32x4v& mid) DYN_INLINE_LAMBDA {
+#pragma unroll
+      for (int p2 = 0; p2 < 4; ++p2) {
+        unsigned h_, m_, l_;
+        split3_pair(v[2 * p2], v[2 * p2 + 1], h_, m_, l_);
+        hi[p2] = h_; mid[p2] = m_;
+      }
+    };
+    u32x4v* Kimg = reinterpret_cast<u32x4v*>(KV);  // [key tile (wave)][group m][hi | mid][64 lanes]
+    f32x16 vnext;                                   // v of the odd head that follows (its projection shares a layer with the even head's)
+    dyn_static_for<4>([&](auto HD) DYN_INLINE_LAMBDA {
+      constexpr int hd = decltype(HD)::value;
+      f32x16 qk[2], vh;
+      acc_zero(qk);
+      PTS8_LAYER(2, 64)(ring, qk, [&](int s) { return g[s / 16][s % 16]; });
+      lds_barrier();  // the previous head's V table is no longer read
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        float kv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) kv[e] = qk[1][8 * m + e];
+        u32x4v khi, kmid;
+        split8(kv, khi, kmid);
+        Kimg[((wave_u * 2 + m) * 2 + 0) * 64 + lane] = khi;
+        Kimg[((wave_u * 2 + m) * 2 + 1) * 64 + lane] = kmid;
+      }
+      u32x4v qhi[2], qmid[2];
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        float qv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qv[e] = qk[0][8 * m + e] * inv_temp;
+        split8(qv, qhi[m], qmid[m]);
+      }
+      // (k is in LDS and q in its split form before the V layer starts: 16 live registers instead of 32 beside the layer's own)
+      if constexpr (hd % 2 == 0) {
+        f32x16 vv2[2];
+        acc_zero(vv2);
+        PTS8_LAYER(2, 64)(ring, vv2, [&](int s) { return g[s / 16][s % 16]; });
+        vh = vv2[0];
+        vnext = vv2[1];
+      } else {
+        vh = vnext;
+      }
+      lds_barrier();
+      f32x16 sc[MAXT];
+      acc_zero(sc);
+#pragma unroll
+      for (int kt = 0; kt < MAXT; ++kt)
+        if (kt < TPR) {
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            const u32x4v ahi = Kimg[(((wave0 + kt) * 2 + m) * 2 + 0) * 64 + lane], amid = Kimg[(((wave0 + kt) * 2 + m) * 2 + 1) * 64 + lane];
+            sc[kt] = mfma_bf16(amid, qhi[m], sc[kt]);
+            sc[kt] = mfma_bf16(ahi, qmid[m], sc[kt]);
+            sc[kt] = mfma_bf16(ahi, qhi[m], sc[kt]);
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (one key tile's K fragments in flight at a time: hoisted together they are 64 registers)
+        }
+      // softmax over the keys; register r of half h is key kt*32 + fi(r,h)   (key tiles beyond the ray's own -- kt >= TPR, a uniform condition -- are skipped)
+      float mx = -3.0e38f;
+#pragma unroll
+      for (int kt = 0; kt < MAXT; ++kt)
+        if (kt < TPR) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const bool key_ok = kt * 32 + dyn_fi(r, h) < p.S;
+            float v = q_ok ? sc[kt][r] : -1e9f;
+            v = key_ok ? v : -3.0e38f;
+            sc[kt][r] = v;
+            mx = fmaxf(mx, v);
+          }
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      float sum = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < MAXT; ++kt)
+        if (kt < TPR) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float e = sc[kt][r] > -1.0e38f ? __expf(sc[kt][r] - mx) : 0.f;
+            sc[kt][r] = e;
+            sum += e;
+          }
+        }
+      sum += __shfl_xor(sum, 32);
+      const float inv = 1.0f / sum;
+      lds_barrier();  // every wave has its scores: the K image makes room for the V table
+#pragma unroll
+      for (int r = 0; r < 16; ++r) KV[dyn_fi(r, h) * SB8_VL_LD + wave_u * 32 + j] = vh[r];
+      lds_barrier();
+      f32x16 oh;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) oh[r] = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < MAXT; ++kt)
+        if (kt < TPR) {
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            // slot e of group m is key kt * 32 + fi(8 m + e, h) = 16 m + 4 h + (e & 3) + 8 (e >> 2): two float4 of this lane's feature row of V^T
+            const float* vrow = KV + j * SB8_VL_LD + (wave0 + kt) * 32 + 16 * m + 4 * h;
+            const float4 v0 = *reinterpret_cast<const float4*>(vrow), v1 = *reinterpret_cast<const float4*>(vrow + 8);
+            const float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+            float pv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) pv[e] = sc[kt][8 * m + e] * inv;
+            u32x4v ahi, amid, phi, pmid;
+            split8(vv, ahi, amid);
+            split8(pv, phi, pmid);
+            oh = mfma_bf16(amid, phi, oh);
+            oh = mfma_bf16(ahi, pmid, oh);
+            oh = mfma_bf16(ahi, phi, oh);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      att[hd] = oh;
+    });
+  }
+  // From here on j, h and what depends on them are worked out again from a copy of the lane number the compiler cannot trace back: it would otherwise
+  // carry them (and the point's index) through the attention, where the lane has no register to spare.
+  int lane_t = lane;
+#if defined(__AMDGCN__)
+  asm volatile("" : "+v"(lane_t));
+#endif
+  const int j_t = lane_t & 31, h_t = lane_t >> 5;
+  const float one_h0_t = h_t == 0 ? 1.0f : 0.0f;
+  {
+    DYN_PHASE(3);  // attention heads done
+    // fc + residual: the accumulators of the layer start at g (beside o, att and the layer's own staging a separate copy of g does not fit the lane's 256 registers)
+    PTS8_LAYER(4, 64)(ring, g, [&](int s) { return att[s / 16][s % 16]; });
+    f32x16 (&o)[4] = g;
+    // LayerNorm(eps = 1e-6) over the 128 features (64 here, 64 in the other half's lane)
+    float s1 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s1 += o[t][r];
+    s1 += __shfl_xor(s1, 32);
+    const float mu = s1 * (1.0f / 128.0f);
+    float s2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float d = o[t][r] - mu;
+        s2 += d * d;
+      }
+    s2 += __shfl_xor(s2, 32);
+    const float rstd = 1.0f / sqrtf(s2 * (1.0f / 128.0f) + 1e-6f);
+    const float* gam = ctab + h_t * 64;
+    const float* bet = ctab + 128 + h_t * 64;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) g[t][r] = (o[t][r] - mu) * rstd * gam[t * 16 + r] + bet[t * 16 + r];
+  }
+  DYN_PHASE(4);  // fc + LayerNorm done
+  const long point = valid ? ray * p.S + kt_self * 32 + j_t : 0;
+  if (!DYN) {
+    f32x16 a[4];
+    acc_zero(a);
+    PTS8_LAYER(4, 65)(ring, a, [&](int s) { return s < 64 ? g[s / 16][s % 16] : one_h0_t; });
+    acc_elu_s(a);
+    float sigma = row_dot<4>(a, ctab + 256) + ctab[384];
+    if (few_views) sigma = -1e9f;
+    if (valid && h_t == 0) p.raw[point * 4 + 3] = sigma;
+    acc_zero(a);
+    PTS8_LAYER(4, 65)(ring, a, [&](int s) { return s < 64 ? g[s / 16][s % 16] : one_h0_t; });
+    if (valid) {
+      float4* dst = reinterpret_cast<float4*>(p.ws + p.o.off_hg) + tile * SB_HG_RECS * 64 + lane;
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dst[(t * 4 + q) * 64] = make_float4(a[t][q * 4], a[t][q * 4 + 1], a[t][q * 4 + 2], a[t][q * 4 + 3]);
+    }
+  } else {
+    // ref_pts_fc([globalfeat, PE(pts)])   (mlp_network.py:289-290)
+    f32x16 g2[4];
+    {
+      f32x16 a8[8];
+      acc_zero(a8);
+      PTS8_LAYER(8, 64)(ring, a8, [&](int s) { return g[s / 16][s % 16]; });
+      float pe[17];  // 15 cos|sin pairs (3 coords x 5 octaves), then (x, y), (z, 1)
+      float c3[3] = {0.f, 0.f, 0.f};
+      if (valid) { c3[0] = p.pts[point * 3]; c3[1] = p.pts[point * 3 + 1]; c3[2] = p.pts[point * 3 + 2]; }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) octave_embed<5>(c3[c], h_t, pe + c * 5);
+      pe[15] = h_t == 0 ? c3[0] : c3[1];
+      pe[16] = h_t == 0 ? c3[2] : 1.0f;
+      PTS8_LAYER(8, 17)(ring, a8, [&](int s) { return pe[s]; });
+      acc_zero(g2);
+      PTS8_LAYER(4, 129)(ring, g2, [&](int s) { return s < 128 ? elu_s(a8[s / 16][s % 16]) : one_h0_t; });
+    }
+    f32x16 a[4];
+    acc_zero(a);
+    PTS8_LAYER(4, 65)(ring, a, [&](int s) {
+      if (s >= 64) return one_h0_t;
+      const float r = elu1(g2[s / 16][s % 16]);  // g2 = ELU(out_geometry_fc.2) is kept: rgb_fc reads it again
+      g2[s / 16][s % 16] = r;
+      return r;
+    });
+    acc_elu_s(a);
+    float sigma = row_dot<4>(a, ctab + 256) + ctab[384] - p.shift;
+    if (few_views) sigma = -1e9f;
+    // rgb_fc([globalfeat, PE(view dir)])   (mlp_network.py:299-313)
+    float pd[14];  // 12 cos|sin pairs (3 coords x 4 octaves), then (dx, dy), (dz, 1)
+    {
+      float d3[3] = {0.f, 0.f, 1.f};
+      if (valid) unit3(p.ray_d[ray * 3], p.ray_d[ray * 3 + 1], p.ray_d[ray * 3 + 2], d3[0], d3[1], d3[2]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) octave_embed<4>(d3[c], h_t, pd + c * 4);
+      pd[12] = h_t == 0 ? d3[0] : d3[1];
+      pd[13] = h_t == 0 ? d3[2] : 1.0f;
+    }
+    acc_zero(a);
+    PTS8_LAYER(4, 78)(ring, a, [&](int s) { return s < 64 ? g2[s / 16][s % 16] : pd[s - 64]; });
+    f32x16 b2[2];
+    acc_zero(b2);
+    PTS8_LAYER(2, 65)(ring, b2, [&](int s) { return s < 64 ? elu_s(a[s / 16][s % 16]) : one_h0_t; });
+    acc_elu_s(b2);
+    float rgb[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      rgb[c] = sigmoid1(row_dot<2>(b2, ctab + 400 + c * 64) + ctab[385 + c]);
+      if (no_view) rgb[c] = 0.f;  // masked_fill(sum(mask) == 0, 0)
+    }
+    if (valid && h_t == 0) reinterpret_cast<float4*>(p.raw)[point] = make_float4(rgb[0], rgb[1], rgb[2], sigma);
+  }
+  DYN_PHASE(20);
+}
+#endif  // DYN_POINTS_DUO
 
 // ===================================================================================================================
 // C: rgb_fc over [globalfeat | x | vis | ray_diff], masked softmax over the views, colour blend
@@ -2163,7 +2465,14 @@ extern "C" int dyn_static_net(const DynStaticNetParams* q, void* stream_) {
   else if (q->V <= 16) DYN_LAUNCH(DYN_K_STATIC_VIEWS, "k_static_views", k_static_views<16>, grid_a, blk_v, lds_a, stream, a);
   else DYN_LAUNCH(DYN_K_STATIC_VIEWS, "k_static_views", k_static_views<32>, grid_a, blk_v, lds_a, stream, a);
   if (a.TPR <= 4) {
-    DYN_LAUNCH(DYN_K_STATIC_POINTS, "k_static_points", (k_net_points<false, 0>), points_grid(grid_b), blk, lds_b, stream, a);
+#if DYN_POINTS_DUO
+    const dim3 grid_b8(dyn_cdiv(a.n_tiles_b, DYN_VIEW_THREADS / 64));
+    const size_t lds_b8 = (PTS_RING_SLOTS * PTS_CHUNK + SB_CT + SB8_KV_FLOATS) * sizeof(float);
+    if (a.TPR <= 2) DYN_LAUNCH(DYN_K_STATIC_POINTS, "k_static_points", (k_net_points_w8<false, 2>), grid_b8, blk_v, lds_b8, stream, a);
+    else DYN_LAUNCH(DYN_K_STATIC_POINTS, "k_static_points", (k_net_points_w8<false, 4>), grid_b8, blk_v, lds_b8, stream, a);
+#else
+    DYN_LAUNCH(DYN_K_STATIC_POINTS, "k_static_points", (k_net_points<false, 0>), grid_b, blk, lds_b, stream, a);
+#endif
   } else {
     DYN_LAUNCH(DYN_K_STATIC_POINTS_QKV, "k_static_points_qkv", (k_net_points<false, 1>), grid_b, blk, lds_b, stream, a);
     DYN_LAUNCH(DYN_K_STATIC_POINTS, "k_static_points", (k_net_points<false, 2>), grid_b, blk, lds_b, stream, a);
@@ -2227,6 +2536,7 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
   pack_net_layer(o, 4, SA_L5_STEPS, scaled(chained(T[DT_VIS2_W], nullptr, 128, 128, 128), DYN_ELU_POST));
   pack_net_layer(o, 4, SA_L5_STEPS, scaled(chained(T[DT_VISB0_W], nullptr, 128, 128, 128), DYN_ELU_PRE));
   DYN_REQUIRE(o.size() == DY_OFF_B, "dynamic pack: A stream size mismatch");
+  const auto pack_b = [&](bool by_head) {
 #if DYN_POINTS_DUO
   g_pack_chunk_pairs = PTS_CP;
 #endif
@@ -2239,9 +2549,13 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
     }, DYN_ELU_PRE));
   }
   pack_net_layer(o, 4, 129, scaled_wb(chained(T[DT_GEO2_W], T[DT_GEO2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0));
-  pack_net_layer(o, 4, 64, chained(T[DT_WQ], nullptr, 128, 128, 128));
-  pack_net_layer(o, 4, 64, chained(T[DT_WK], nullptr, 128, 128, 128));
-  pack_net_layer(o, 4, 64, chained(T[DT_WV], nullptr, 128, 128, 128));
+  if (by_head) {
+    pack_qkv_by_head(o, T[DT_WQ], T[DT_WK], T[DT_WV]);
+  } else {
+    pack_net_layer(o, 4, 64, chained(T[DT_WQ], nullptr, 128, 128, 128));
+    pack_net_layer(o, 4, 64, chained(T[DT_WK], nullptr, 128, 128, 128));
+    pack_net_layer(o, 4, 64, chained(T[DT_WV], nullptr, 128, 128, 128));
+  }
   pack_net_layer(o, 4, 64, chained(T[DT_FC], nullptr, 128, 128, 128));
   {
     const float *W = T[DT_REFPTS0_W], *b = T[DT_REFPTS0_B];  // [256, 128 + 33]
@@ -2267,6 +2581,8 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
   }
   pack_net_layer(o, 2, 65, scaled_wb(chained(T[DT_RGB2_W], T[DT_RGB2_B], 64, 128, 128), 64, DYN_ELU_POST * DYN_ELU_PRE, DYN_ELU_PRE));
   g_pack_chunk_pairs = B6_CHUNK_PAIRS;
+  };
+  pack_b(false);
   DYN_REQUIRE(o.size() == DY_OFF_CTA, "dynamic pack: B stream size mismatch");
   pack_rowtab(o, T[DT_VIS2_W] + 128 * 128, 128, DYN_ELU_POST);
   pack_rowtab(o, T[DT_VISB2_W], 128, DYN_ELU_POST);
@@ -2298,7 +2614,11 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
   for (int i = 0; i < 256; ++i) o.push_back(T[DT_RAYDIR0_B][i]);
   for (int i = 0; i < 35 * 256; ++i) o.push_back(T[DT_RAYDIR2_W][i]);
   for (int i = 0; i < 35; ++i) o.push_back(T[DT_RAYDIR2_B][i]);
-  o.resize(DY_BLOB_FLOATS, 0.f);
+  o.resize(DY_OFF_B8, 0.f);
+#if DYN_POINTS_DUO
+  pack_b(true);
+#endif
+  DYN_REQUIRE(o.size() == DY_BLOB_FLOATS, "dynamic pack: B8 stream size mismatch");
   DYN_REQUIRE(!g_pack_range_error, "dyn_dynamic_net_pack: a weight is outside the half-float range of the split engine (|w| >= 65504 or not finite)");
   for (size_t i = 0; i < DY_BLOB_FLOATS; ++i) blob[i] = o[i];
   return 0;
@@ -2412,7 +2732,14 @@ extern "C" int dyn_dynamic_net(const DynDynamicNetParams* q, void* stream_) {
   else if (q->V <= 16) DYN_LAUNCH(DYN_K_DYNAMIC_VIEWS, "k_dynamic_views", k_dynamic_views<16>, grid_a, blk_v, lds_a, stream, a);
   else DYN_LAUNCH(DYN_K_DYNAMIC_VIEWS, "k_dynamic_views", k_dynamic_views<32>, grid_a, blk_v, lds_a, stream, a);
   if (a.TPR <= 4) {
-    DYN_LAUNCH(DYN_K_DYNAMIC_POINTS, "k_dynamic_points", (k_net_points<true, 0>), points_grid(grid_b), blk, lds_b, stream, a);
+#if DYN_POINTS_DUO
+    const dim3 grid_b8(dyn_cdiv(a.n_tiles_b, DYN_VIEW_THREADS / 64));
+    const size_t lds_b8 = (PTS_RING_SLOTS * PTS_CHUNK + DB_CT + SB8_KV_FLOATS) * sizeof(float);
+    if (a.TPR <= 2) DYN_LAUNCH(DYN_K_DYNAMIC_POINTS, "k_dynamic_points", (k_net_points_w8<true, 2>), grid_b8, blk_v, lds_b8, stream, a);
+    else DYN_LAUNCH(DYN_K_DYNAMIC_POINTS, "k_dynamic_points", (k_net_points_w8<true, 4>), grid_b8, blk_v, lds_b8, stream, a);
+#else
+    DYN_LAUNCH(DYN_K_DYNAMIC_POINTS, "k_dynamic_points", (k_net_points<true, 0>), grid_b, blk, lds_b, stream, a);
+#endif
   } else {
     DYN_LAUNCH(DYN_K_DYNAMIC_POINTS_QKV, "k_dynamic_points_qkv", (k_net_points<true, 1>), grid_b, blk, lds_b, stream, a);
     DYN_LAUNCH(DYN_K_DYNAMIC_POINTS, "k_dynamic_points", (k_net_points<true, 2>), grid_b, blk, lds_b, stream, a);
