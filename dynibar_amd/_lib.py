@@ -14,7 +14,18 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'dynibar_hip.h')
-LIB_PATH = os.environ.get('DYNIBAR_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libdynibar_hip.so')  # env: developer A/B builds
+# The engine flavours of the library (dynibar_amd.engine): one file each, a process binds one of them.
+ENGINE_LIBS = {'split': 'libdynibar_hip.so', 'exact': 'libdynibar_hip_x6.so', 'half': 'libdynibar_hip_x1.so'}
+
+
+def engine_path(name):
+  if name not in ENGINE_LIBS:
+    raise ValueError(f'unknown engine {name!r}: one of {", ".join(ENGINE_LIBS)}')
+  return os.path.join(_HERE, 'csrc', ENGINE_LIBS[name])
+
+
+# DYNIBAR_HIP_LIB (an explicit path: developer A/B builds) wins over DYNIBAR_ENGINE (a flavour by name) wins over the default flavour
+LIB_PATH = os.environ.get('DYNIBAR_HIP_LIB') or engine_path(os.environ.get('DYNIBAR_ENGINE') or 'split')
 
 _CTYPES = {
     'int': ctypes.c_int, 'float': ctypes.c_float, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
@@ -101,6 +112,11 @@ def lib():
     if ver != 1:
       raise RuntimeError(f'libdynibar_hip.so ABI {ver} != 1')
   return _LIB
+
+
+def bound_path():
+  """The file of the library this process has bound (None before the first lib() call)."""
+  return getattr(_LIB, '_name', None) if _LIB is not None else None
 
 
 def _install_for_tests(cdll, require_device):

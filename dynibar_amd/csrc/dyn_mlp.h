@@ -240,21 +240,35 @@ __device__ __forceinline__ float row_dot(const f32x16 (&act)[NTI], const float* 
 #ifndef DYN_SPLIT_F16
 #define DYN_SPLIT_F16 1
 #endif
-#if DYN_SPLIT_F16 && DYN_SPLIT_TERMS != 3
-#error "the half-float split engine has two parts per operand (DYN_SPLIT_TERMS == 3)"
+#if DYN_SPLIT_F16 && DYN_SPLIT_TERMS == 6
+#error "the half-float engine has one or two parts per operand (DYN_SPLIT_TERMS == 1 or 3)"
 #endif
-#if DYN_SPLIT_TERMS == 3
+#if !DYN_SPLIT_F16 && DYN_SPLIT_TERMS == 1
+#error "the one-product engine multiplies IEEE halves (DYN_SPLIT_F16 == 1)"
+#endif
+// DYN_SPLIT_TERMS = 1 (the x1 build, "half" engine): ONE half per operand and one MFMA per (k-group, tile) pair -- the 10 explicit mantissa bits of the TF32
+// tensor cores the reference's own A100 runs multiplied with, fp32 accumulation.  Weights round to nearest even on the host, activations round to nearest
+// even in one packed convert per pair (NOT the truncating convert of the split engine's first part: without a second part to absorb the residual, truncation
+// is a bias that grows with K) and saturate at +-65504.  A pair is one 1 KiB image, a chunk is still 48 KiB.  A bias that rides in a k-slot whose other
+// half is free is packed as two halves (hi in half 0, the residual in half 1) against a 1 in BOTH halves (DYN_BIAS_ONE), so it stays fp32-class.
+#if DYN_SPLIT_TERMS == 1
+#define DYN_SPLIT_PARTS 1
+#define B6_CHUNK_PAIRS 48
+#elif DYN_SPLIT_TERMS == 3
 #define DYN_SPLIT_PARTS 2
 #define B6_CHUNK_PAIRS 24
 #elif DYN_SPLIT_TERMS == 6
 #define DYN_SPLIT_PARTS 3
 #define B6_CHUNK_PAIRS 16
 #else
-#error "DYN_SPLIT_TERMS must be 3 or 6"
+#error "DYN_SPLIT_TERMS must be 1, 3 or 6"
 #endif
+// the activation that multiplies a bias k-slot, for a lane of half h: 1 in half 0 (the bias), and in the one-product build 1 in half 1 too (the bias's residual)
+#define DYN_BIAS_ONE(h) ((DYN_SPLIT_TERMS == 1 || (h) == 0) ? 1.0f : 0.0f)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
@@ -359,13 +373,29 @@ __device__ __forceinline__ void ring6_piece(const WeightRing6& R, int k) {
 }
 // pair `pr` of the `npc` pairs of the chunk being consumed: pieces of the next chunk due by now (all of them by two thirds of the chunk, so that
 // the last one has a third of a chunk to land before the barrier that publishes it)
+// B6_FEED_STATELESS: which pieces pair `pr` hands out follows from (pr, npc) alone -- the pieces due after pair pr - 1 are out already, the layer loop
+// calls this for every pair in order -- instead of from the running count R.issued.  The same pieces at the same pairs; but with 48 pairs per chunk (the
+// one-product build) hipcc no longer follows R.issued through the unrolled chunk, keeps the hand-out as run-time loops and the accumulators in scratch memory.
+#ifndef B6_FEED_STATELESS
+#define B6_FEED_STATELESS (DYN_SPLIT_TERMS == 1 ? 1 : 0)
+#endif
 __device__ __forceinline__ void ring6_feed(WeightRing6& R, int pr, int npc) {
   if (R.fill < 0) return;
   const int n = ring6_pieces(R);
   const int den = (B6_DMA_WINDOW_NUM * npc + B6_DMA_WINDOW_DEN - 1) / B6_DMA_WINDOW_DEN > 0 ? (B6_DMA_WINDOW_NUM * npc + B6_DMA_WINDOW_DEN - 1) / B6_DMA_WINDOW_DEN : 1;
   int want = (n * (pr + 1) + den - 1) / den;
   if (want > n) want = n;
+#if B6_FEED_STATELESS
+  int prev = (n * pr + den - 1) / den;  // what pair pr - 1 wanted (0 for the first pair)
+  if (prev > n) prev = n;
+#pragma unroll
+  for (int k = 0; k < 12; ++k)  // (12: the pieces per wave and chunk at four waves, the fewest a ring runs with)
+    if (k >= prev && k < want) ring6_piece(R, k);
+  for (int k = prev > 12 ? prev : 12; k < want; ++k) ring6_piece(R, k);  // (a ring of fewer waves: never taken at 4 or 8)
+  R.issued = want;
+#else
   for (; R.issued < want; ++R.issued) ring6_piece(R, R.issued);
+#endif
 }
 
 __device__ __forceinline__ void ring6_issue(const WeightRing6& R, int chunk) {
@@ -494,7 +524,13 @@ __device__ __forceinline__ void ring6_prio_flip(const WeightRing6& R, int phase)
 }
 // exact three-way bf16 split of two fp32 values, each part packed as (first in the low half, second in the high half)
 __device__ __forceinline__ void split3_pair(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-#if DYN_SPLIT_F16
+#if DYN_SPLIT_TERMS == 1
+  // one part: clamp to the largest half (a finite operand never becomes inf), then one packed convert in the default rounding mode (to nearest even)
+  const f32x2v v = {__builtin_amdgcn_fmed3f(a, -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(b, -65504.0f, 65504.0f)};
+  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2v));
+  mid = 0u;
+  lo = 0u;
+#elif DYN_SPLIT_F16
   // truncating pack-convert (one instruction per pair), exact residuals (<= 13 significant bits), truncating pack-convert again
   const auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
   hi = __builtin_bit_cast(unsigned, h);
@@ -548,7 +584,10 @@ struct B6A {
 __device__ __forceinline__ B6A b6_load_a(const float* pair, int lane) {
   const u32x4v* w = reinterpret_cast<const u32x4v*>(pair) + lane;
   B6A a;
-  a.hi = w[0]; a.mid = w[64];
+  a.hi = w[0];
+#if DYN_SPLIT_PARTS >= 2
+  a.mid = w[64];
+#endif
 #if DYN_SPLIT_PARTS == 3
   a.lo = w[128];
 #endif
@@ -631,8 +670,10 @@ __device__ __forceinline__ void mlp_layer_b6(WeightRing6& R, f32x16 (&acc)[NT], 
         acc[t] = mfma_bf16(cur.hi, bl, acc[t]);
         acc[t] = mfma_bf16(cur.mid, bm, acc[t]);
 #endif
+#if DYN_SPLIT_TERMS != 1
         acc[t] = mfma_bf16(cur.mid, bh, acc[t]);
         acc[t] = mfma_bf16(cur.hi, bm, acc[t]);
+#endif
         acc[t] = mfma_bf16(cur.hi, bh, acc[t]);
         if (t == NT - 1) { bh = nh; bm = nm; bl = nl; }
         __builtin_amdgcn_sched_barrier(0);
@@ -897,18 +938,18 @@ __device__ __forceinline__ void mlp_layer_b6_duo(WeightRing3& R, f32x16 (&acc)[N
     acc[t0] = mfma_bf16(a0.mid, bm, acc[t0]);
     if (U == 2) acc[t1] = mfma_bf16(a1.mid, bm, acc[t1]);
 #endif
-    acc[t0] = mfma_bf16(a0.mid, bh, acc[t0]);
+    if (DYN_SPLIT_TERMS != 1) acc[t0] = mfma_bf16(a0.mid, bh, acc[t0]);
     if (U == 2) {
       if (P + AHEAD + 1 < NP) q[(P + AHEAD + 1) % QN] = load(P + AHEAD + 1);
       gap(1);
-      acc[t1] = mfma_bf16(a1.mid, bh, acc[t1]);
+      if (DYN_SPLIT_TERMS != 1) acc[t1] = mfma_bf16(a1.mid, bh, acc[t1]);
       gap(2);
     }
-    acc[t0] = mfma_bf16(a0.hi, bm, acc[t0]);
+    if (DYN_SPLIT_TERMS != 1) acc[t0] = mfma_bf16(a0.hi, bm, acc[t0]);
     if (U == 2) {
       gap(3);
       dma(1);
-      acc[t1] = mfma_bf16(a1.hi, bm, acc[t1]);
+      if (DYN_SPLIT_TERMS != 1) acc[t1] = mfma_bf16(a1.hi, bm, acc[t1]);
       gap(4);
     }
     acc[t0] = mfma_bf16(a0.hi, bh, acc[t0]);
@@ -972,22 +1013,22 @@ __device__ __forceinline__ void mlp_layer_b6_duo(WeightRing3& R, f32x16 (&acc)[N
     acc[t0] = mfma_pinned<ACC_AGPR>(a0.mid, bm, acc[t0]);
     if constexpr (U == 2) acc[t1] = mfma_pinned<ACC_AGPR>(a1.mid, bm, acc[t1]);
 #endif
-    acc[t0] = mfma_pinned<ACC_AGPR>(a0.mid, bh, acc[t0]);
+    if constexpr (DYN_SPLIT_TERMS != 1) acc[t0] = mfma_pinned<ACC_AGPR>(a0.mid, bh, acc[t0]);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (U == 2) {
       // ---- gap 1
       if constexpr (P + AHEAD + 1 < NP) q[(P + AHEAD + 1) % QN] = load(P + AHEAD + 1);
       gap(std::integral_constant<int, 1>{});
-      acc[t1] = mfma_pinned<ACC_AGPR>(a1.mid, bh, acc[t1]);
+      if constexpr (DYN_SPLIT_TERMS != 1) acc[t1] = mfma_pinned<ACC_AGPR>(a1.mid, bh, acc[t1]);
       __builtin_amdgcn_sched_barrier(0);
       gap(std::integral_constant<int, 2>{});
     }
-    acc[t0] = mfma_pinned<ACC_AGPR>(a0.hi, bm, acc[t0]);
+    if constexpr (DYN_SPLIT_TERMS != 1) acc[t0] = mfma_pinned<ACC_AGPR>(a0.hi, bm, acc[t0]);
     if constexpr (U == 2) {
       __builtin_amdgcn_sched_barrier(0);
       gap(std::integral_constant<int, 3>{});
       dma(std::integral_constant<int, 1>{});
-      acc[t1] = mfma_pinned<ACC_AGPR>(a1.hi, bm, acc[t1]);
+      if constexpr (DYN_SPLIT_TERMS != 1) acc[t1] = mfma_pinned<ACC_AGPR>(a1.hi, bm, acc[t1]);
       __builtin_amdgcn_sched_barrier(0);
       gap(std::integral_constant<int, 4>{});
     }
@@ -1045,8 +1086,10 @@ __device__ __forceinline__ void mlp_layer_b6_lds(const float* w, f32x16 (&acc)[N
     acc[t] = mfma_bf16(cur.hi, bl, acc[t]);
     acc[t] = mfma_bf16(cur.mid, bm, acc[t]);
 #endif
+#if DYN_SPLIT_TERMS != 1
     acc[t] = mfma_bf16(cur.mid, bh, acc[t]);
     acc[t] = mfma_bf16(cur.hi, bm, acc[t]);
+#endif
     acc[t] = mfma_bf16(cur.hi, bh, acc[t]);
     if (t == NT - 1) { bh = nh; bm = nm; bl = nl; }
     __builtin_amdgcn_sched_barrier(0);
@@ -1081,8 +1124,10 @@ __device__ __forceinline__ void b6_tile_apply(const B6TileW<NSLOTS>& w, f32x16& 
     acc = mfma_bf16(w.a[g].hi, bl, acc);
     acc = mfma_bf16(w.a[g].mid, bm, acc);
 #endif
+#if DYN_SPLIT_TERMS != 1
     acc = mfma_bf16(w.a[g].mid, bh, acc);
     acc = mfma_bf16(w.a[g].hi, bm, acc);
+#endif
     acc = mfma_bf16(w.a[g].hi, bh, acc);
   }
 }

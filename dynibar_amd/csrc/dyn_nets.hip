@@ -25,9 +25,12 @@ namespace {
 // value of the packed A operand for (output tile t, row i, k-step s, half h)
 using SlotFn = std::function<float(int t, int i, int s, int h)>;
 
-// B6 engine image of one layer (dyn_mlp.h): per (k-group of 8 slots, output tile) three lane-linear 1 KiB parts [hi | mid | lo]
+// B6 engine image of one layer (dyn_mlp.h): per (k-group of 8 slots, output tile) DYN_SPLIT_PARTS lane-linear 1 KiB parts [hi (| mid (| lo))].
+// ones_slot: the k-slot that carries the bias in half 0 against nothing in half 1 (-1: none).  The one-product build stores the bias there as two halves,
+// its rounded value in half 0 and the rounded residual in half 1 (the kernels feed DYN_BIAS_ONE to both); the split builds ignore it.
+thread_local bool g_pack_slot_error = false;  // set when a layer names a bias slot (ones_slot) whose half 1 already carries a weight
 thread_local int g_pack_chunk_pairs = B6_CHUNK_PAIRS;  // pairs per chunk of the stream being packed (the point kernels' streams use PTS_CP); per host thread: two threads may pack at once
-void pack_layer_b6(std::vector<float>& out, int NT, int NSLOTS, const SlotFn& fn) {
+void pack_layer_b6(std::vector<float>& out, int NT, int NSLOTS, const SlotFn& fn, int ones_slot = -1) {
   const int CPAIRS = g_pack_chunk_pairs, CFLOATS = CPAIRS * B6_PAIR_FLOATS;
   const int NG = (NSLOTS + 7) / 8, GPC = CPAIRS / NT, NCH = (NG + GPC - 1) / GPC;
   const size_t base = out.size();
@@ -42,19 +45,21 @@ void pack_layer_b6(std::vector<float>& out, int NT, int NSLOTS, const SlotFn& fn
           for (int e = 0; e < 8; ++e) {
             const int s = g * 8 + e;
             if (s >= NSLOTS) continue;
-            const float w = fn(t, lane & 31, s, lane >> 5);
+            const bool two_half_bias = DYN_SPLIT_PARTS == 1 && s == ones_slot;
+            if (two_half_bias && fn(t, lane & 31, s, 1) != 0.f) g_pack_slot_error = true;  // half 1 of the bias slot must be free
+            const float w = fn(t, lane & 31, s, two_half_bias ? 0 : lane >> 5);
             unsigned short hi, mid, lo;
             split_weight(w, hi, mid, lo);
             const size_t pair = (size_t)c * CFLOATS * 2 + (size_t)(gi * NT + t) * B6_PAIR_FLOATS * 2;  // in 16-bit units
-            img[pair + 0 * 512 + lane * 8 + e] = hi;
-            img[pair + 1 * 512 + lane * 8 + e] = mid;
+            img[pair + 0 * 512 + lane * 8 + e] = two_half_bias && (lane >> 5) == 1 ? mid : hi;
+            if (DYN_SPLIT_PARTS >= 2) img[pair + 1 * 512 + lane * 8 + e] = mid;
             if (DYN_SPLIT_PARTS == 3) img[pair + 2 * 512 + lane * 8 + e] = lo;
           }
     }
 }
 
-void pack_net_layer(std::vector<float>& out, int NT, int NSLOTS, const SlotFn& fn) {
-  pack_layer_b6(out, NT, NSLOTS, fn);
+void pack_net_layer(std::vector<float>& out, int NT, int NSLOTS, const SlotFn& fn, int ones_slot = -1) {
+  pack_layer_b6(out, NT, NSLOTS, fn, ones_slot);
 }
 
 // input feature of a chained layer: k-step s, half h -> feature of the previous layer's output (D layout)
@@ -133,7 +138,7 @@ constexpr int SA_CHUNKS = net_layer_chunks(8, SA_L1P_STEPS) + net_layer_chunks(8
 // streams are packed in chunks of PTS_CP = 16 pairs (32 KiB; 3 slots = 96 KiB, what the two 48 KiB slots took).  DYN_POINTS_DUO = 0: the round-3 form (A/B builds;
 // the 6-term bf16 build keeps it, on k_net_points for every ray length: its pairs are 3 KiB).
 #ifndef DYN_POINTS_DUO
-#define DYN_POINTS_DUO (DYN_SPLIT_TERMS == 3 ? 1 : 0)
+#define DYN_POINTS_DUO (DYN_SPLIT_TERMS != 6 ? 1 : 0)
 #endif
 #if DYN_POINTS_DUO
 #define PTS_CP 16
@@ -239,6 +244,7 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
   for (int i = 0; i < ST_NUM_TENSORS; ++i) DYN_REQUIRE(T[i] != nullptr, "dyn_static_net_pack: tensor %d is NULL", i);
   std::vector<float> o;
   g_pack_range_error = false;
+  g_pack_slot_error = false;
   o.reserve(ST_BLOB_FLOATS);
   // ---- A ----
   {
@@ -251,7 +257,7 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
     pack_net_layer(o, 8, SA_L1V_STEPS, scaled([=](int t, int i, int s, int h) -> float {
       const int n = 32 * t + i, c = sa_l1v_col(s, h);
       return c >= 0 ? W[n * 103 + c] : (c == -2 ? b[n] : 0.f);
-    }, DYN_ELU_PRE));
+    }, DYN_ELU_PRE), 35);  // (slot 35: ONE | -)
   }
   pack_net_layer(o, 2, SA_L2_STEPS, scaled(chained(T[ST_RAYDIR2_W], nullptr, 35, 256, 256), DYN_ELU_POST));
   {
@@ -267,7 +273,7 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
       if (s == SA_NX) return h == 0 ? b[n] : 0.f;
       const int c = sa_c70(s, h);
       return c < 0 ? 0.f : W[n * 210 + 140 + c];
-    }, DYN_ELU_PRE));
+    }, DYN_ELU_PRE), SA_NX);
   }
   pack_net_layer(o, 4, SA_L4_STEPS, scaled(chained(T[ST_BASE2_W], nullptr, 128, 256, 256), DYN_ELU_POST));
   pack_net_layer(o, 4, SA_L5_STEPS, scaled(chained(T[ST_VIS0_W], nullptr, 128, 128, 128), DYN_ELU_PRE));
@@ -287,7 +293,7 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
       return h == 0 ? W[n * 257 + 256] : b[n];                                          // mean of the weights | bias
     }, DYN_ELU_PRE));
   }
-  pack_net_layer(o, 4, 129, scaled_wb(chained(T[ST_GEO2_W], T[ST_GEO2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0));
+  pack_net_layer(o, 4, 129, scaled_wb(chained(T[ST_GEO2_W], T[ST_GEO2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0), 128);
   if (by_head) {
     pack_qkv_by_head(o, T[ST_WQ], T[ST_WK], T[ST_WV]);
   } else {
@@ -296,8 +302,8 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
     pack_net_layer(o, 4, 64, chained(T[ST_WV], nullptr, 128, 128, 128));
   }
   pack_net_layer(o, 4, 64, chained(T[ST_FC], nullptr, 128, 128, 128));
-  pack_net_layer(o, 4, 65, scaled(chained(T[ST_OG0_W], T[ST_OG0_B], 128, 128, 128), DYN_ELU_PRE));
-  pack_net_layer(o, 4, 65, scaled(chained(T[ST_RGB0_W], T[ST_RGB0_B], 128, 128, 261), DYN_ELU_PRE));  // columns 0..127 = globalfeat part
+  pack_net_layer(o, 4, 65, scaled(chained(T[ST_OG0_W], T[ST_OG0_B], 128, 128, 128), DYN_ELU_PRE), 64);
+  pack_net_layer(o, 4, 65, scaled(chained(T[ST_RGB0_W], T[ST_RGB0_B], 128, 128, 261), DYN_ELU_PRE), 64);  // columns 0..127 = globalfeat part
   g_pack_chunk_pairs = B6_CHUNK_PAIRS;
   };
   pack_b(false);
@@ -348,6 +354,7 @@ extern "C" int dyn_static_net_pack(const float* const* T, int F, float* blob, si
   pack_b(true);
 #endif
   DYN_REQUIRE(o.size() == ST_BLOB_FLOATS, "static pack: B8 stream size mismatch");
+  DYN_REQUIRE(!g_pack_slot_error, "dyn_static_net_pack: a layer's bias slot carries a weight in its second half (the one-product build stores the bias residual there)");
   DYN_REQUIRE(!g_pack_range_error, "dyn_static_net_pack: a weight is outside the half-float range of the split engine (|w| >= 65504 or not finite)");
   for (size_t i = 0; i < ST_BLOB_FLOATS; ++i) blob[i] = o[i];
   return 0;
@@ -402,7 +409,7 @@ struct StaticWs {
 #define SB_HG_RECS 16   // point part of rgb_fc.0 per (point, half)
 
 #ifndef DYN_BLEND_WS
-#define DYN_BLEND_WS (DYN_SPLIT_TERMS == 3 ? 1 : 0)
+#define DYN_BLEND_WS (DYN_SPLIT_TERMS != 6 ? 1 : 0)
 #endif
 static bool ragged_rows_enabled() {
   static const int off = getenv("DYN_RAGGED") ? (atoi(getenv("DYN_RAGGED")) == 0) : 0;  // developer A/B: DYN_RAGGED=0 evaluates every row (rounds 1-5)
@@ -965,7 +972,7 @@ __device__ __forceinline__ void base_fc0(NetRing& ring, const float* pooled_w, c
   constexpr int PHASE_KID = 0;
   (void)PHASE_KID;
   const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5, wave = threadIdx.x >> 6;
-  const float one_h0 = h == 0 ? 1.0f : 0.0f;
+  const float one_h0 = DYN_BIAS_ONE(h);
   if constexpr (VSEG == 0) {
     // dense rows: the statistics come through the LDS tables, the rest is the pooled form below with col = the point's index in the workgroup
     float* res = pool + POOL_FLOATS(NX);
@@ -1341,7 +1348,7 @@ __global__ void __launch_bounds__(DYN_VIEW_THREADS, 2) k_static_views(StaticArgs
     in1[32] = h0 ? c6[4] : c6[5];
     in1[33] = h0 ? rd.x : rd.y;
     in1[34] = h0 ? rd.z : rd.w;
-    in1[35] = h0 ? 1.0f : 0.0f;
+    in1[35] = DYN_BIAS_ONE(h0 ? 0 : 1);
     DYN_PHASE(1);
     net_layer<8, SA_L1V_STEPS>(ring, a1, [&](int s) { return in1[s]; });
     DYN_PHASE(2);
@@ -1460,7 +1467,7 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
   lds_barrier();
 
   const int TPR = p.TPR;
-  const float one_h0 = h == 0 ? 1.0f : 0.0f;
+  const float one_h0 = DYN_BIAS_ONE(h);
   const long tile = (long)blockIdx.x * 4 + wave;
   const long ray = tile / TPR;
   const int kt_self = (int)(tile - ray * TPR);
@@ -1650,7 +1657,9 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
         u32x4v khi, kmid;
         split8(kv, khi, kmid);
         Kimg[((wave * 2 + m) * 2 + 0) * 64 + lane] = khi;
+#if DYN_SPLIT_PARTS >= 2
         Kimg[((wave * 2 + m) * 2 + 1) * 64 + lane] = kmid;
+#endif
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) Vl[dyn_fi(r, h) * SB_VL_LD + wave * 32 + j] = vh[hd][r];
@@ -1670,9 +1679,12 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
         if (kt < TPR) {
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
-            const u32x4v ahi = Kimg[(((wave0 + kt) * 2 + m) * 2 + 0) * 64 + lane], amid = Kimg[(((wave0 + kt) * 2 + m) * 2 + 1) * 64 + lane];
+            const u32x4v ahi = Kimg[(((wave0 + kt) * 2 + m) * 2 + 0) * 64 + lane];
+#if DYN_SPLIT_TERMS != 1
+            const u32x4v amid = Kimg[(((wave0 + kt) * 2 + m) * 2 + 1) * 64 + lane];
             sc[kt] = mfma_bf16(amid, qhi[m], sc[kt]);
             sc[kt] = mfma_bf16(ahi, qmid[m], sc[kt]);
+#endif
             sc[kt] = mfma_bf16(ahi, qhi[m], sc[kt]);
           }
         }
@@ -1723,8 +1735,10 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 1) k_net_points(StaticArgs p)
             u32x4v ahi, amid, phi, pmid;
             split8(vv, ahi, amid);
             split8(pv, phi, pmid);
+#if DYN_SPLIT_TERMS != 1
             oh = mfma_bf16(amid, phi, oh);
             oh = mfma_bf16(ahi, pmid, oh);
+#endif
             oh = mfma_bf16(ahi, phi, oh);
           }
         }
@@ -1880,7 +1894,7 @@ __global__ void __launch_bounds__(DYN_VIEW_THREADS, 2) k_net_points_w8(StaticArg
   // Everything about the tile is wave-uniform and lives in scalar registers; what a lane needs of its point at the very end (its index) is worked out
   // again there, and num_valid_obs is kept as the three conditions it decides: the chain has no registers to carry per-lane values through.
   const int TPR = p.TPR;  // 1, 2 or 4 here, <= MAXT
-  const float one_h0 = h == 0 ? 1.0f : 0.0f;
+  const float one_h0 = DYN_BIAS_ONE(h);
 #if defined(__AMDGCN__)
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 #else
@@ -1973,7 +1987,9 @@ __global__ void __launch_bounds__(DYN_VIEW_THREADS, 2) k_net_points_w8(StaticArg
         u32x4v khi, kmid;
         split8(kv, khi, kmid);
         Kimg[((wave_u * 2 + m) * 2 + 0) * 64 + lane] = khi;
+#if DYN_SPLIT_PARTS >= 2
         Kimg[((wave_u * 2 + m) * 2 + 1) * 64 + lane] = kmid;
+#endif
       }
       u32x4v qhi[2], qmid[2];
 #pragma unroll
@@ -2001,9 +2017,12 @@ __global__ void __launch_bounds__(DYN_VIEW_THREADS, 2) k_net_points_w8(StaticArg
         if (kt < TPR) {
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
-            const u32x4v ahi = Kimg[(((wave0 + kt) * 2 + m) * 2 + 0) * 64 + lane], amid = Kimg[(((wave0 + kt) * 2 + m) * 2 + 1) * 64 + lane];
+            const u32x4v ahi = Kimg[(((wave0 + kt) * 2 + m) * 2 + 0) * 64 + lane];
+#if DYN_SPLIT_TERMS != 1
+            const u32x4v amid = Kimg[(((wave0 + kt) * 2 + m) * 2 + 1) * 64 + lane];
             sc[kt] = mfma_bf16(amid, qhi[m], sc[kt]);
             sc[kt] = mfma_bf16(ahi, qmid[m], sc[kt]);
+#endif
             sc[kt] = mfma_bf16(ahi, qhi[m], sc[kt]);
           }
           __builtin_amdgcn_sched_barrier(0);  // (one key tile's K fragments in flight at a time: hoisted together they are 64 registers)
@@ -2058,8 +2077,10 @@ __global__ void __launch_bounds__(DYN_VIEW_THREADS, 2) k_net_points_w8(StaticArg
             u32x4v ahi, amid, phi, pmid;
             split8(vv, ahi, amid);
             split8(pv, phi, pmid);
+#if DYN_SPLIT_TERMS != 1
             oh = mfma_bf16(amid, phi, oh);
             oh = mfma_bf16(ahi, pmid, oh);
+#endif
             oh = mfma_bf16(ahi, phi, oh);
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -2074,7 +2095,7 @@ __global__ void __launch_bounds__(DYN_VIEW_THREADS, 2) k_net_points_w8(StaticArg
   asm volatile("" : "+v"(lane_t));
 #endif
   const int j_t = lane_t & 31, h_t = lane_t >> 5;
-  const float one_h0_t = h_t == 0 ? 1.0f : 0.0f;
+  const float one_h0_t = DYN_BIAS_ONE(h_t);
   {
     DYN_PHASE(3);  // attention heads done
     // fc + residual: the accumulators of the layer start at g (beside o, att and the layer's own staging a separate copy of g does not fit the lane's 256 registers)
@@ -2517,6 +2538,7 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
   for (int i = 0; i < DT_NUM_TENSORS; ++i) DYN_REQUIRE(T[i] != nullptr, "dyn_dynamic_net_pack: tensor %d is NULL", i);
   std::vector<float> o;
   g_pack_range_error = false;
+  g_pack_slot_error = false;
   o.reserve(DY_BLOB_FLOATS);
   {
     const float *W = T[DT_BASE0_W], *b = T[DT_BASE0_B];  // input [mean | var | x]  (mlp_network.py:262-266)
@@ -2529,7 +2551,7 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
       if (s == DA_NX) return h == 0 ? b[n] : 0.f;
       const int c = da_c35(s, h);
       return c < 0 ? 0.f : W[n * 105 + 70 + c];
-    }, DYN_ELU_PRE));
+    }, DYN_ELU_PRE), DA_NX);
   }
   pack_net_layer(o, 4, SA_L4_STEPS, scaled(chained(T[DT_BASE2_W], nullptr, 128, 256, 256), DYN_ELU_POST));
   pack_net_layer(o, 4, SA_L5_STEPS, scaled(chained(T[DT_VIS0_W], nullptr, 128, 128, 128), DYN_ELU_PRE));
@@ -2548,7 +2570,7 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
       return h == 0 ? W[n * 257 + 256] : b[n];
     }, DYN_ELU_PRE));
   }
-  pack_net_layer(o, 4, 129, scaled_wb(chained(T[DT_GEO2_W], T[DT_GEO2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0));
+  pack_net_layer(o, 4, 129, scaled_wb(chained(T[DT_GEO2_W], T[DT_GEO2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0), 128);
   if (by_head) {
     pack_qkv_by_head(o, T[DT_WQ], T[DT_WK], T[DT_WV]);
   } else {
@@ -2567,8 +2589,8 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
       return h == 0 ? W[n * 161 + 128 + 2] : b[n];
     }, DYN_ELU_PRE));
   }
-  pack_net_layer(o, 4, 129, scaled_wb(chained(T[DT_REFPTS2_W], T[DT_REFPTS2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0));
-  pack_net_layer(o, 4, 65, scaled(chained(T[DT_OG0_W], T[DT_OG0_B], 128, 128, 128), DYN_ELU_PRE));
+  pack_net_layer(o, 4, 129, scaled_wb(chained(T[DT_REFPTS2_W], T[DT_REFPTS2_B], 128, 256, 256), 128, DYN_ELU_POST, 1.0), 128);
+  pack_net_layer(o, 4, 65, scaled(chained(T[DT_OG0_W], T[DT_OG0_B], 128, 128, 128), DYN_ELU_PRE), 64);
   {
     const float *W = T[DT_RGB0_W], *b = T[DT_RGB0_B];  // [128, 128 + 27]
     pack_net_layer(o, 4, 78, scaled([=](int t, int i, int s, int h) -> float {
@@ -2579,7 +2601,7 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
       return h == 0 ? W[n * 155 + 128 + 2] : b[n];
     }, DYN_ELU_PRE));
   }
-  pack_net_layer(o, 2, 65, scaled_wb(chained(T[DT_RGB2_W], T[DT_RGB2_B], 64, 128, 128), 64, DYN_ELU_POST * DYN_ELU_PRE, DYN_ELU_PRE));
+  pack_net_layer(o, 2, 65, scaled_wb(chained(T[DT_RGB2_W], T[DT_RGB2_B], 64, 128, 128), 64, DYN_ELU_POST * DYN_ELU_PRE, DYN_ELU_PRE), 64);
   g_pack_chunk_pairs = B6_CHUNK_PAIRS;
   };
   pack_b(false);
@@ -2619,6 +2641,7 @@ extern "C" int dyn_dynamic_net_pack(const float* const* T, int F, float* blob, s
   pack_b(true);
 #endif
   DYN_REQUIRE(o.size() == DY_BLOB_FLOATS, "dynamic pack: B8 stream size mismatch");
+  DYN_REQUIRE(!g_pack_slot_error, "dyn_dynamic_net_pack: a layer's bias slot carries a weight in its second half (the one-product build stores the bias residual there)");
   DYN_REQUIRE(!g_pack_range_error, "dyn_dynamic_net_pack: a weight is outside the half-float range of the split engine (|w| >= 65504 or not finite)");
   for (size_t i = 0; i < DY_BLOB_FLOATS; ++i) blob[i] = o[i];
   return 0;
@@ -2774,6 +2797,7 @@ extern "C" int dyn_motion_mlp_pack(const float* const* T, int num_basis, float* 
   for (int i = 0; i < MT_NUM_TENSORS; ++i) DYN_REQUIRE(T[i] != nullptr, "dyn_motion_mlp_pack: tensor %d is NULL", i);
   std::vector<float> o;
   g_pack_range_error = false;
+  g_pack_slot_error = false;
   o.reserve(MO_BLOB_FLOATS);
   {
     const float *W = T[MT_L0_W], *b = T[MT_L0_B];
@@ -2781,9 +2805,9 @@ extern "C" int dyn_motion_mlp_pack(const float* const* T, int num_basis, float* 
       const int n = 32 * t + i;
       if (s < MO_PE_STEPS) return W[n * 132 + mo_pe_col(s, h)];
       return h == 0 ? b[n] : 0.f;
-    });
+    }, MO_PE_STEPS);
   }
-  for (int l = 1; l <= 4; ++l) pack_net_layer(o, 8, 129, chained(T[MT_L0_W + 2 * l], T[MT_L0_B + 2 * l], 256, 256, 256));
+  for (int l = 1; l <= 4; ++l) pack_net_layer(o, 8, 129, chained(T[MT_L0_W + 2 * l], T[MT_L0_B + 2 * l], 256, 256, 256), 128);
   {
     const float *W = T[MT_L5_W], *b = T[MT_L5_B];  // input = cat([embedding(132), h(256)])
     pack_net_layer(o, 8, MO_PE_STEPS + 129, [=](int t, int i, int s, int h) -> float {
@@ -2792,17 +2816,18 @@ extern "C" int dyn_motion_mlp_pack(const float* const* T, int num_basis, float* 
       const int s2 = s - MO_PE_STEPS;
       if (s2 < 128) return W[n * 388 + 132 + chain_feature(s2, h)];
       return h == 0 ? b[n] : 0.f;
-    });
+    }, MO_PE_STEPS + 128);
   }
-  pack_net_layer(o, 8, 129, chained(T[MT_L6_W], T[MT_L6_B], 256, 256, 256));
-  pack_net_layer(o, 8, 129, chained(T[MT_L7_W], T[MT_L7_B], 256, 256, 256));
-  pack_net_layer(o, 1, 129, chained(T[MT_COEFF_W], T[MT_COEFF_B], 3 * num_basis, 256, 256));
+  pack_net_layer(o, 8, 129, chained(T[MT_L6_W], T[MT_L6_B], 256, 256, 256), 128);
+  pack_net_layer(o, 8, 129, chained(T[MT_L7_W], T[MT_L7_B], 256, 256, 256), 128);
+  pack_net_layer(o, 1, 129, chained(T[MT_COEFF_W], T[MT_COEFF_B], 3 * num_basis, 256, 256), 128);
   DYN_REQUIRE(o.size() == MO_OFF_FREQ, "motion pack: stream size mismatch");
   {
     // torch.linspace(1, 17, 16) in fp32: start + i * step below the midpoint, end - (n - 1 - i) * step above it
     const float step = (17.0f - 1.0f) / 15.0f;
     for (int i = 0; i < 16; ++i) o.push_back(i < 8 ? 1.0f + (float)i * step : 17.0f - (float)(15 - i) * step);
   }
+  DYN_REQUIRE(!g_pack_slot_error, "dyn_motion_mlp_pack: a layer's bias slot carries a weight in its second half (the one-product build stores the bias residual there)");
   DYN_REQUIRE(!g_pack_range_error, "dyn_motion_mlp_pack: a weight is outside the half-float range of the split engine (|w| >= 65504 or not finite)");
   for (size_t i = 0; i < MO_BLOB_FLOATS; ++i) blob[i] = o[i];
   return 0;
@@ -2875,7 +2900,7 @@ k_motion_mlp(const float* __restrict__ blob, const float* __restrict__ pts, cons
   float c4[4] = {0.f, 0.f, 0.f, time[0]};
   if (valid) { c4[0] = pts[point * 3]; c4[1] = pts[point * 3 + 1]; c4[2] = pts[point * 3 + 2]; }
   const float* freq = blob + MO_OFF_FREQ;
-  const float one_h0 = h == 0 ? 1.0f : 0.0f;
+  const float one_h0 = DYN_BIAS_ONE(h);
   f32x16 a[8], b[8];
   // the embedding feeds layer 0 and the skip layer: evaluated once and kept (one wave per SIMD: 512 registers per lane to spend)
   float pe[MO_PE_STEPS];
@@ -2931,7 +2956,7 @@ extern "C" int dyn_motion_mlp(const float* blob, const float* pts, const float* 
 extern "C" int dyn_mlp_split_terms(void) {
   return DYN_SPLIT_TERMS;
 }
-extern "C" int dyn_mlp_split_kind(void) {  // 0: native fp32 MFMA, 1: bf16 parts, 2: half-float parts
+extern "C" int dyn_mlp_split_kind(void) {  // 0: native fp32 MFMA, 1: bf16 parts, 2: half-float parts (two in the default build, one in the x1 build)
 #if DYN_SPLIT_F16
   return 2;
 #else
@@ -2952,7 +2977,7 @@ __global__ void __launch_bounds__(DYN_NET_THREADS, 2) k_selftest(const float* __
   f32x16 in[2];
 #pragma unroll
   for (int s = 0; s < 32; ++s) in[s / 16][s % 16] = row < rows ? x[row * 64 + 32 * (s / 16) + dyn_fi(s % 16, h)] : 0.f;
-  const float one_h0 = h == 0 ? 1.0f : 0.0f;
+  const float one_h0 = DYN_BIAS_ONE(h);
 #pragma unroll
   for (int rep = 0; rep < 2; ++rep) {  // two chained applications of the same layer
     f32x16 acc[2];
@@ -2971,8 +2996,8 @@ extern "C" int dyn_mlp_selftest(const float* W, const float* b, const float* x, 
   // W [64,64], b [64]: HOST; x [rows,64], y [rows,64], stream_buf [2 * chunks * 4096]: DEVICE (stream_buf is filled here via hipMemcpy)
   DYN_REQUIRE(W && b && x && y && stream_buf && rows > 0, "dyn_mlp_selftest: bad argument");
   std::vector<float> o;
-  pack_net_layer(o, 2, 33, chained(W, b, 64, 64, 64));
-  pack_net_layer(o, 2, 33, chained(W, b, 64, 64, 64));
+  pack_net_layer(o, 2, 33, chained(W, b, 64, 64, 64), 32);
+  pack_net_layer(o, 2, 33, chained(W, b, 64, 64, 64), 32);
   if (hipMemcpy(stream_buf, o.data(), o.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
     dyn_set_error("dyn_mlp_selftest: hipMemcpy failed");
     return DYN_E_LAUNCH;

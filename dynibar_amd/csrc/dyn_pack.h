@@ -59,7 +59,13 @@ static thread_local bool g_pack_range_error = false;  // set when a weight does 
 
 // one weight -> the engine's parts (hi | mid | lo as 16-bit patterns)
 inline void split_weight(float w, unsigned short& hi, unsigned short& mid, unsigned short& lo) {
-#if DYN_SPLIT_F16
+#if DYN_SPLIT_F16 && DYN_SPLIT_PARTS == 1
+  // the one-product engine: one half per weight, to nearest even (`mid` = the rounded residual: only a two-half bias slot stores it)
+  if (!(fabsf(w) < 65504.0f)) g_pack_range_error = true;
+  hi = f16_rne(w);
+  mid = f16_rne(w - f16_to_f32(hi));
+  lo = 0;
+#elif DYN_SPLIT_F16
   if (!(fabsf(w) < 65504.0f)) g_pack_range_error = true;
   hi = f16_rne(w);
   const float r1 = w - f16_to_f32(hi);

@@ -280,9 +280,10 @@ int dyn_enc_in_apply(const float* x, const double* stats, const float* gamma, co
 int dyn_enc_in_bwd(const float* dy, const float* y, int relu, const float* x, const double* stats, const float* gamma, int N, long HW, double* sums2,
                    float* dx, float* dres, float* dgamma, float* dbeta, void* stream);
 
-/* ---- how the network kernels of this build multiply (csrc/dyn_mlp.h): split terms = partial products kept per fp32 product (3 or 6;
+/* ---- how the network kernels of this build multiply (csrc/dyn_mlp.h): split terms = partial products kept per fp32 product (1, 3 or 6;
  * 0 = native fp32 MFMA engine); split kind = what the operand parts are: 0 none (fp32 MFMA), 1 bf16 (3 terms: 16 mantissa bits per
- * operand; 6 terms: fp32-class), 2 IEEE half (3 terms: 22 mantissa bits per operand, fp32-class; the shipped engine) --------------- */
+ * operand; 6 terms: fp32-class), 2 IEEE half (3 terms: 22 mantissa bits per operand, fp32-class; the shipped engine.  1 term: one half
+ * per operand, the 11 significant bits of TF32 -- libdynibar_hip_x1.so, the `half` engine of dynibar_amd.engine) --------------- */
 int dyn_mlp_split_terms(void);
 int dyn_mlp_split_kind(void);
 
