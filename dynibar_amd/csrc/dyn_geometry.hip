@@ -38,7 +38,7 @@ static const char* const g_prof_names[DYN_K_COUNT] = {
     "k_static_points_qkv", "k_dynamic_points_qkv", "k_enc_conv7", "k_enc_conv3", "k_enc_conv1", "k_enc_block_out",
     "k_train_gemm", "k_train_rows", "k_train_attn", "k_gather_bwd", "k_motion_zero_tail", "k_ragged_plan",
     "k_splat_project", "k_splat_keys", "k_splat_sort", "k_splat_resolve", "k_sobel_alpha", "k_vv_finish",
-    "k_objective_fwd", "k_objective_bwd", "k_metrics_tile", "k_metrics_finish"};
+    "k_objective_fwd", "k_objective_bwd", "k_metrics_tile", "k_metrics_finish", "k_scene_views", "k_scene_supervision"};
 
 static void prof_flush(int slot) {
   for (int i = 0; i < g_prof.used[slot]; ++i) {
@@ -1554,24 +1554,42 @@ extern "C" int dyn_expected_scene_flow(const float* weights, const float* coeff,
 // ---------------------------------------------------------------------------------------------------------------
 // a2 all-pixel rays of a target view (sample_ray.py:143-163): d = c2w[:3,:3] . inv(K[:3,:3]) . [u, v, 1], o = c2w[:3,3]
 // ---------------------------------------------------------------------------------------------------------------
-__global__ void k_image_rays(const float* __restrict__ camera, int Ws, int n, int stride, float* __restrict__ rays_o, float* __restrict__ rays_d) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// The ray of one pixel in two steps, shared with k_scene_supervision (dyn_scene.h): the selected rays of a training batch have the bits
+// that dyn_image_rays gives those pixels.  K [4,4] and c2w [4,4] row-major (camera + 2, camera + 18).
+struct DynRayBasis {
+  float m[3][3];  // fp32(R . inv(K3))
+  float o[3];
+};
+__device__ __forceinline__ void dyn_ray_basis(const float* __restrict__ K4, const float* __restrict__ c2w, DynRayBasis& out) {
   // M = R . inv(K3) in double (the reference inverts K with LAPACK in fp32; agreement is to ~1e-7 relative, not bitwise)
   double K[9], Rm[9], Ki[9];
   for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) { K[a * 3 + b] = camera[2 + a * 4 + b]; Rm[a * 3 + b] = camera[18 + a * 4 + b]; }
+    for (int b = 0; b < 3; ++b) { K[a * 3 + b] = K4[a * 4 + b]; Rm[a * 3 + b] = c2w[a * 4 + b]; }
   const double det = K[0] * (K[4] * K[8] - K[5] * K[7]) - K[1] * (K[3] * K[8] - K[5] * K[6]) + K[2] * (K[3] * K[7] - K[4] * K[6]);
   Ki[0] = (K[4] * K[8] - K[5] * K[7]) / det; Ki[1] = (K[2] * K[7] - K[1] * K[8]) / det; Ki[2] = (K[1] * K[5] - K[2] * K[4]) / det;
   Ki[3] = (K[5] * K[6] - K[3] * K[8]) / det; Ki[4] = (K[0] * K[8] - K[2] * K[6]) / det; Ki[5] = (K[2] * K[3] - K[0] * K[5]) / det;
   Ki[6] = (K[3] * K[7] - K[4] * K[6]) / det; Ki[7] = (K[1] * K[6] - K[0] * K[7]) / det; Ki[8] = (K[0] * K[4] - K[1] * K[3]) / det;
-  const float u = (float)((i % Ws) * stride), v = (float)((i / Ws) * stride);
   for (int a = 0; a < 3; ++a) {
-    const float m0 = (float)(Rm[a * 3] * Ki[0] + Rm[a * 3 + 1] * Ki[3] + Rm[a * 3 + 2] * Ki[6]);
-    const float m1 = (float)(Rm[a * 3] * Ki[1] + Rm[a * 3 + 1] * Ki[4] + Rm[a * 3 + 2] * Ki[7]);
-    const float m2 = (float)(Rm[a * 3] * Ki[2] + Rm[a * 3 + 1] * Ki[5] + Rm[a * 3 + 2] * Ki[8]);
-    rays_d[i * 3 + a] = fmaf(m0, u, fmaf(m1, v, m2));
-    rays_o[i * 3 + a] = camera[18 + a * 4 + 3];
+    out.m[a][0] = (float)(Rm[a * 3] * Ki[0] + Rm[a * 3 + 1] * Ki[3] + Rm[a * 3 + 2] * Ki[6]);
+    out.m[a][1] = (float)(Rm[a * 3] * Ki[1] + Rm[a * 3 + 1] * Ki[4] + Rm[a * 3 + 2] * Ki[7]);
+    out.m[a][2] = (float)(Rm[a * 3] * Ki[2] + Rm[a * 3 + 1] * Ki[5] + Rm[a * 3 + 2] * Ki[8]);
+    out.o[a] = c2w[a * 4 + 3];
+  }
+}
+__device__ __forceinline__ void dyn_ray_dir(const DynRayBasis& b, float u, float v, float (&d)[3]) {
+  for (int a = 0; a < 3; ++a) d[a] = fmaf(b.m[a][0], u, fmaf(b.m[a][1], v, b.m[a][2]));
+}
+__global__ void k_image_rays(const float* __restrict__ camera, int Ws, int n, int stride, float* __restrict__ rays_o, float* __restrict__ rays_d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  DynRayBasis b;
+  dyn_ray_basis(camera + 2, camera + 18, b);
+  const float u = (float)((i % Ws) * stride), v = (float)((i / Ws) * stride);
+  float d[3];
+  dyn_ray_dir(b, u, v, d);
+  for (int a = 0; a < 3; ++a) {
+    rays_d[i * 3 + a] = d[a];
+    rays_o[i * 3 + a] = b.o[a];
   }
 }
 extern "C" int dyn_image_rays(const float* camera, int H, int W, int render_stride, float* rays_o, float* rays_d, void* stream) {
@@ -1920,3 +1938,4 @@ extern "C" int dyn_plucker_src(const float* pts, int per_view_pts, const float* 
 // forward splatting of the virtual source views (render_source_vv.py) -- its own header, this unit's flags
 #include "dyn_splat.h"
 #include "dyn_metrics.h"
+#include "dyn_scene.h"

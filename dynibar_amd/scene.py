@@ -1,0 +1,412 @@
+"""Training batches assembled on the device from a scene that is uploaded once.
+
+The reference builds ``ray_batch`` in three host steps per iteration: ``MonocularDataset.__getitem__`` (ibrnet/data_loaders/monocular.py:146-425)
+decodes about 30 images in a DataLoader worker and stacks them as float32, ``RaySamplerSingleImage`` builds all ``H*W`` rays, and
+``random_sample`` (sample_ray.py:262-331) gathers the supervision with fancy indexing and copies about twenty tensors to the device.  Here the
+scene lives on the device as uint8 / fp32 stores and an iteration's batch is two kernel launches (csrc/dyn_scene.h) driven by a few dozen
+integers:
+
+    scene = DeviceScene(device, images, intrinsics, poses, depth_range, disp, motion_mask, static_mask, flows, flow_masks,
+                        virtual_views, virtual_poses, source_masks)              # once per scene
+    plan = scene.plan(epoch, args)                 # replaces the DataLoader's __getitem__: the same draws from np.random in the same order
+    train_data = plan['train_data']                # id, anchor_id, ref_time, anchor_time, nearest_pose_ids, ... as train.py reads them
+    ray_sampler = scene.sampler(plan)              # replaces RaySamplerSingleImage(train_data, device)
+    ray_batch = ray_sampler.random_sample(N_rand, sample_mode=..., center_ratio=...)
+
+``random_sample`` and ``get_all`` return what ``dynibar_amd.sample_ray.RaySamplerSingleImage`` returns for the collated dictionary of the same
+frame: the same keys, shapes, dtypes and bits.  The pixel indices come from ``sample_ray.rng`` by ``sample_random_pixel``'s own logic, so the
+reference's index stream is unchanged and shared with the host sampler.
+
+What stays host work of the caller, once per scene: reading and decoding the files, ``cv2.resize``, the disk erosion of the motion mask
+(monocular.py:177-204) and ``disp / scale``.  cv2, skimage and imageio were not available when this was written, so their semantics are not
+restated here: the arrays are taken as the caller's own loader produces them.
+
+Host traffic per batch: the plan's descriptors and the pixel indices go through one pinned staging buffer -- one asynchronous host-to-device
+copy, no device-to-host copy and no synchronisation.  There is no CPU fallback: without the library or a HIP device this module raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib, sample_ray
+from ._lib import call, params, stream_of
+from .train_static import POISON_SCRATCH
+
+MAX_VIEWS = 32       # per source-view list: the network engine's own limit (dyn_scene_views refuses more)
+NUM_VIRTUAL = 8      # virtual views per frame (monocular.py:313)
+FLOW_OFFSETS = (1, 2, 3, -1, -2, -3)  # the order of flows / flow_masks along their second axis (monocular.py:216, :249-263)
+_STAGE_SLOTS = 4     # pinned staging buffers in rotation: a slot is rewritten only after the copy that read it has completed
+
+
+def _p(t):
+  return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _np(x, what):
+  if isinstance(x, torch.Tensor):
+    x = x.detach().cpu().numpy()
+  if not isinstance(x, np.ndarray):
+    raise ValueError(f'{what} must be a numpy array or a torch tensor, got {type(x).__name__}')
+  return x
+
+
+def _host_tensor(x):
+  """the array as a host tensor without a copy (a read-only array is only read: uploaded)"""
+  with warnings.catch_warnings():
+    warnings.simplefilter('ignore', UserWarning)
+    return torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _shape(x, want, what):
+  if tuple(x.shape) != tuple(want):
+    raise ValueError(f'{what} must be {list(want)}, got {list(x.shape)}')
+  return x
+
+
+def _binary_u8(x, want, what):
+  """a 0 / 1 mask given as uint8, bool or float32 -> uint8 0 / 1"""
+  x = _shape(_np(x, what), want, what)
+  if x.dtype not in (np.uint8, np.bool_, np.float32):
+    raise ValueError(f'{what} must be uint8, bool or float32, got {x.dtype}')
+  if x.dtype != np.bool_ and not np.logical_or(x == 0, x == 1).all():
+    raise ValueError(f'{what} must hold only 0 and 1')
+  return np.ascontiguousarray(x.astype(np.uint8))
+
+
+def nearest_pose_ids_dist(tar_pose, ref_poses, tar_id):
+  """``get_nearest_pose_ids(tar_pose, ref_poses, tar_id=tar_id, angular_dist_method='dist')`` (ibrnet/data_loaders/data_utils.py:85-120)"""
+  num_cams = len(ref_poses)
+  batched_tar_pose = tar_pose[None, ...].repeat(num_cams, 0)
+  tar_cam_locs = batched_tar_pose[:, :3, 3]
+  ref_cam_locs = ref_poses[:, :3, 3]
+  dists = np.linalg.norm(tar_cam_locs - ref_cam_locs, axis=1)
+  if tar_id >= 0:
+    assert tar_id < num_cams
+    dists[tar_id] = 1e3
+  return np.argsort(dists)
+
+
+class DeviceScene(object):
+  """One monocular scene of ``N >= 7`` frames, resident on ``device``.
+
+  images         uint8 ``[N, H, W, 3]``: the decoded frames (the reference divides them by 255 per iteration; the kernels do it on the fly)
+  intrinsics     ``[N, 4, 4]``, poses ``[N, 4, 4]`` camera-to-world (``batch_parse_llff_poses``); cast to float32 for the cameras like
+                 ``load_src_view`` does, kept as given for the view selection
+  depth_range    ``(near, far)``: becomes ``[near * 0.9, far * 1.5]``, computed in double and then cast to float32 (monocular.py:396-398)
+  disp           float32 ``[N, H, W]``, already divided by the scene's scale
+  motion_mask, static_mask   ``[N, H, W]``, flow_masks ``[N, 6, H, W]``: 0 / 1 as uint8, bool or float32 (after the caller's resize / erosion)
+  flows          float32 ``[N, 6, H, W, 2]``; flows and flow_masks in the order of the offsets +1, +2, +3, -1, -2, -3
+  virtual_views  uint8 ``[N, 8, H, W, 3]``, virtual_poses ``[N, 8, 4, 4]`` (``batch_parse_vv_poses``)
+  source_masks   None, or the masks ``args.mask_src_view`` multiplies the static source views by (monocular.py:131-142): uint8 ``[N, H, W]``
+                 or ``[N, H, W, 3]`` as decoded, 0..255 (the view is multiplied by ``m / 255``); bool or float32 0 / 1 are stored as 0 / 255
+
+  Decoding, ``cv2.resize``, the erosion and ``disp / scale`` are the caller's (module docstring).  Bad shapes or dtypes raise ValueError."""
+
+  def __init__(self, device, images, intrinsics, poses, depth_range, disp, motion_mask, static_mask, flows, flow_masks, virtual_views,
+               virtual_poses, source_masks=None):
+    self.device = torch.device(device)
+    images = _np(images, 'images')
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
+      raise ValueError(f'images must be uint8 [N, H, W, 3], got {images.dtype} {list(images.shape)}')
+    N, H, W = (int(v) for v in images.shape[:3])
+    if N < 7:
+      raise ValueError(f'a scene needs at least 7 frames (the first and the last 3 are never targets), got {N}')
+    if H < 1 or W < 1 or H * W * 3 >= 2 ** 31:
+      raise ValueError(f'image size {H} x {W} is unsupported (H*W*3 < 2^31)')
+    self.N, self.H, self.W = N, H, W
+    self.intrinsics_host = _shape(_np(intrinsics, 'intrinsics'), (N, 4, 4), 'intrinsics')
+    self.poses_host = _shape(_np(poses, 'poses'), (N, 4, 4), 'poses')
+    disp = _shape(_np(disp, 'disp'), (N, H, W), 'disp')
+    flows = _shape(_np(flows, 'flows'), (N, 6, H, W, 2), 'flows')
+    for x, what in ((disp, 'disp'), (flows, 'flows')):
+      if x.dtype != np.float32:
+        raise ValueError(f'{what} must be float32, got {x.dtype}')
+    motion_mask = _binary_u8(motion_mask, (N, H, W), 'motion_mask')
+    static_mask = _binary_u8(static_mask, (N, H, W), 'static_mask')
+    flow_masks = _binary_u8(flow_masks, (N, 6, H, W), 'flow_masks')
+    virtual_views = _shape(_np(virtual_views, 'virtual_views'), (N, NUM_VIRTUAL, H, W, 3), 'virtual_views')
+    if virtual_views.dtype != np.uint8:
+      raise ValueError(f'virtual_views must be uint8, got {virtual_views.dtype}')
+    virtual_poses = _shape(_np(virtual_poses, 'virtual_poses'), (N, NUM_VIRTUAL, 4, 4), 'virtual_poses')
+    mask_channels = 1
+    if source_masks is not None:
+      source_masks = _np(source_masks, 'source_masks')
+      if tuple(source_masks.shape) not in ((N, H, W), (N, H, W, 3)):
+        raise ValueError(f'source_masks must be [{N}, {H}, {W}] or [{N}, {H}, {W}, 3], got {list(source_masks.shape)}')
+      if source_masks.dtype != np.uint8:
+        source_masks = _binary_u8(source_masks, source_masks.shape, 'source_masks') * np.uint8(255)
+      mask_channels = 3 if source_masks.ndim == 4 else 1
+    if self.device.type != 'cuda' and _lib._REQUIRE_DEVICE:
+      raise ValueError(f'DeviceScene needs a HIP device (cuda:N), got {self.device}: there is no CPU fallback')
+    near, far = depth_range
+    self.depth_range = torch.tensor([[near * 0.9, far * 1.5]]).float().to(self.device)  # [1, 2]: the collated form
+
+    dev = self.device
+    self._frames, image_stride = self._padded(images.reshape(N, -1))
+    self._vviews = self._padded(virtual_views.reshape(N * NUM_VIRTUAL, -1))[0]
+    self._src_masks, mask_stride = self._padded(source_masks.reshape(N, -1)) if source_masks is not None else (None, 0)
+    f32 = lambda x: _host_tensor(x.astype(np.float32, copy=False)).to(dev)
+    u8 = lambda x: _host_tensor(x).to(dev)
+    self._intrinsics = f32(self.intrinsics_host.reshape(N, 16))
+    self._poses = f32(self.poses_host.reshape(N, 16))
+    self._vposes = f32(virtual_poses.reshape(N, NUM_VIRTUAL, 16))
+    self._disp, self._flows = f32(disp), f32(flows)
+    self._motion_mask, self._static_mask, self._flow_masks = u8(motion_mask), u8(static_mask), u8(flow_masks)
+    self.has_source_masks = source_masks is not None
+    self._store = params('DynSceneStore', N=N, H=H, W=W, image_stride=image_stride, frames=_p(self._frames), vviews=_p(self._vviews),
+                         src_masks=_p(self._src_masks), mask_channels=mask_channels, mask_stride=mask_stride, intrinsics=_p(self._intrinsics),
+                         poses=_p(self._poses), vposes=_p(self._vposes), disp=_p(self._disp), motion_mask=_p(self._motion_mask),
+                         static_mask=_p(self._static_mask), flows=_p(self._flows), flow_masks=_p(self._flow_masks))
+    self._stage_slots = [None] * _STAGE_SLOTS
+    self._stage_next = 0
+
+  def _padded(self, rows):
+    """uint8 [n, bytes] -> the device store [n, stride], stride = bytes rounded up to 16 (zero padding), and the stride"""
+    n, nbytes = rows.shape
+    stride = (nbytes + 15) // 16 * 16
+    store = torch.zeros((n, stride), dtype=torch.uint8, device=self.device)
+    store[:, :nbytes] = _host_tensor(rows).to(self.device)
+    return store, stride
+
+  # ---- view selection (host only) -------------------------------------------------------------------------------------------------
+  def plan(self, epoch, args, rng=np.random):
+    """The view selection of ``MonocularDataset.__getitem__`` (monocular.py:146-298, :313, :375) for one iteration, restated literally: the same
+    draws from ``rng`` in the same order.  args: ``num_source_views``, ``max_range``, ``init_decay_epoch``, ``num_vv``, ``mask_src_view``.
+    -> dict: ``idx``, ``anchor_idx``, ``nearest_pose_ids``, ``anchor_nearest_pose_ids``, ``static_pose_ids``, ``ref_virtual``, ``anchor_virtual``,
+    ``counts`` (views in the ref, anchor and static lists), ``desc`` (int32 ``[V, 4]`` for dyn_scene_views: image frame, virtual index or -1, mask
+    frame or -1, intrinsics frame) and ``train_data``, the non-image entries of the collated item that train.py reads."""
+    num_frames = self.N
+    num_frames_sample = int(args.num_source_views)
+    num_vv = int(args.num_vv)
+    mask_src_view = bool(getattr(args, 'mask_src_view', False))
+    if num_vv < 0 or num_vv > NUM_VIRTUAL:
+      raise ValueError(f'num_vv={num_vv}: a frame has {NUM_VIRTUAL} virtual views')
+    if mask_src_view and not self.has_source_masks:
+      raise ValueError('args.mask_src_view is set but the scene was made without source_masks')
+    if num_frames_sample < 1 or 2 * num_frames_sample > MAX_VIEWS:
+      raise ValueError(f'num_source_views={num_frames_sample}: the static list holds up to twice as many views, at most {MAX_VIEWS}')
+    # skip first and last 3 frames
+    idx = int(rng.randint(3, num_frames - 3))
+    # view selection based on time interval
+    nearest_pose_ids = [idx + offset for offset in [1, 2, 3, -1, -2, -3]]
+    max_step = min(3, epoch // (args.init_decay_epoch) + 1)
+    # select a nearby time index for cross time rendering
+    anchor_pool = [i for i in range(1, max_step + 1)] + [-i for i in range(1, max_step + 1)]
+    anchor_idx = int(idx + anchor_pool[rng.choice(len(anchor_pool))])
+    anchor_nearest_pose_ids = []
+    for offset in [3, 2, 1, 0, -1, -2, -3]:
+      if (anchor_idx + offset) < 0 or (anchor_idx + offset) >= num_frames or (anchor_idx + offset) == idx:
+        continue
+      anchor_nearest_pose_ids.append((anchor_idx + offset))
+    # occasionally include render image for anchor time index
+    if rng.choice([0, 1], p=[1.0 - 0.005, 0.005]):
+      anchor_nearest_pose_ids.append(idx)
+    anchor_nearest_pose_ids = np.sort(anchor_nearest_pose_ids)
+
+    sp_pose_ids = nearest_pose_ids_dist(self.poses_host[idx], self.poses_host, idx)
+    static_pose_ids = []
+    max_interval = args.max_range // num_frames_sample
+    interval = rng.randint(max(2, max_interval - 2), max_interval + 1)
+    for ii in range(-num_frames_sample, num_frames_sample):
+      rand_j = rng.randint(1, interval + 1)
+      static_pose_id = idx + interval * ii + rand_j
+      if 0 <= static_pose_id < num_frames and static_pose_id != idx:
+        static_pose_ids.append(static_pose_id)
+    static_pose_set = set(static_pose_ids)
+    # if there are no enough image, add nearest images w.r.t camera poses; stride of 5 so that views are not very close to each other
+    for sp_pose_id in sp_pose_ids[::5]:
+      if len(static_pose_ids) >= (num_frames_sample * 2):
+        break
+      if sp_pose_id not in static_pose_set:
+        static_pose_ids.append(sp_pose_id)
+    static_pose_ids = np.sort(static_pose_ids)
+    ref_virtual = rng.choice(list(range(0, 8)), size=num_vv, replace=False)
+    anchor_virtual = rng.choice(list(range(0, 8)), size=num_vv, replace=False)
+
+    desc, counts = self.descriptors(idx, anchor_idx, nearest_pose_ids, anchor_nearest_pose_ids, static_pose_ids, ref_virtual, anchor_virtual,
+                                    mask_src_view)
+    train_data = {  # what default_collate makes of the item's scalars and id lists (batch size 1)
+        'id': torch.tensor([idx]), 'anchor_id': torch.tensor([anchor_idx]), 'num_frames': torch.tensor([num_frames]),
+        'ref_time': torch.tensor([float(idx / float(num_frames))], dtype=torch.float64),
+        'anchor_time': torch.tensor([float(anchor_idx / float(num_frames))], dtype=torch.float64),
+        'nearest_pose_ids': torch.from_numpy(np.array(nearest_pose_ids))[None],
+        'anchor_nearest_pose_ids': torch.from_numpy(np.array(anchor_nearest_pose_ids))[None],
+    }
+    return dict(idx=idx, anchor_idx=anchor_idx, nearest_pose_ids=nearest_pose_ids, anchor_nearest_pose_ids=anchor_nearest_pose_ids,
+                static_pose_ids=static_pose_ids, ref_virtual=ref_virtual, anchor_virtual=anchor_virtual, counts=counts, desc=desc,
+                train_data=train_data)
+
+  def descriptors(self, idx, anchor_idx, nearest_pose_ids, anchor_nearest_pose_ids, static_pose_ids, ref_virtual, anchor_virtual, mask_src_view):
+    """The three source-view lists of monocular.py:300-394 as dyn_scene_views descriptors -> (int32 ``[V, 4]``, (ref, anchor, static) sizes)."""
+    idx, anchor_idx = int(idx), int(anchor_idx)
+    ref_list = [(int(i), -1, -1, int(i)) for i in nearest_pose_ids] + [(idx, int(v), -1, idx) for v in ref_virtual]
+    # (the anchor's virtual views carry the intrinsics of frame idx, not of the anchor: monocular.py:385-389)
+    anchor_list = [(int(i), -1, -1, int(i)) for i in anchor_nearest_pose_ids] + [(anchor_idx, int(v), -1, idx) for v in anchor_virtual]
+    static_list = [(int(i), -1, int(i) if mask_src_view else -1, int(i)) for i in static_pose_ids]
+    counts = (len(ref_list), len(anchor_list), len(static_list))
+    if min(counts) == 0:
+      raise ValueError(f'an empty source-view list: {counts} views in the ref, anchor and static lists')
+    if max(counts) > MAX_VIEWS:
+      raise ValueError(f'{max(counts)} views in a list: more than {MAX_VIEWS}')
+    return np.asarray(ref_list + anchor_list + static_list, dtype=np.int32).reshape(-1, 4), counts
+
+  def sampler(self, plan):
+    return DeviceRaySampler(self, plan)
+
+  # ---- one batch ------------------------------------------------------------------------------------------------------------------
+  def _stage(self, n):
+    """-> (int32 host buffer of >= n entries, its completion event or None).  Pinned buffers in rotation; a slot whose last copy is still in
+    flight is waited for (with _STAGE_SLOTS batches in between that copy finished long ago: no wait happens in a training loop)."""
+    on_device = self.device.type == 'cuda'
+    if any(s is None or s[0].numel() < n for s in self._stage_slots):  # (all slots at once: after the first batch nothing is allocated)
+      cap = max(1024, 1 << (n - 1).bit_length())
+      for j, s in enumerate(self._stage_slots):
+        if s is not None and s[1] is not None and s[2][0]:
+          s[1].synchronize()
+        self._stage_slots[j] = (torch.empty((cap,), dtype=torch.int32, pin_memory=on_device), torch.cuda.Event() if on_device else None, [False])
+    i = self._stage_next
+    self._stage_next = (i + 1) % _STAGE_SLOTS
+    slot = self._stage_slots[i]
+    buf, ev, used = slot
+    if ev is not None and used[0] and not ev.query():
+      ev.synchronize()
+    return slot
+
+  def assemble(self, desc, counts, frame, anchor_frame, sel):
+    """The two launches of one batch.  desc int32 ``[V, 4]``, counts the sizes of the three lists, sel the pixel indices (None: all ``H*W``).
+    -> (images ``[V, H, W, 3]``, cameras ``[V, 34]``, dict of the per-pixel tensors and the two cameras).  Nothing synchronises."""
+    H, W, dev = self.H, self.W, self.device
+    desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 4)
+    V = int(desc.shape[0])
+    counts = tuple(int(c) for c in counts)
+    if len(counts) != 3 or sum(counts) != V or V < 1:
+      raise ValueError(f'view lists of {counts} for {V} descriptors')
+    if max(counts) > MAX_VIEWS:
+      raise ValueError(f'{max(counts)} views in a list: more than {MAX_VIEWS}')
+    R = H * W if sel is None else int(len(sel))
+    if R < 1:
+      raise ValueError('no pixel selected')
+    n = 4 * V + (0 if sel is None else R)
+    host, ev, used = self._stage(n)
+    stage = host.numpy()
+    stage[:4 * V] = desc.reshape(-1)
+    if sel is not None:
+      sel = np.asarray(sel)
+      if sel.size and (sel.min() < -2 ** 31 or sel.max() >= 2 ** 31):
+        raise ValueError('pixel index out of range')
+      stage[4 * V:n] = sel
+    ints = torch.empty((n,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev) if dev.type == 'cuda' else _Null():
+      ints.copy_(host[:n], non_blocking=True)  # the batch's one host-to-device copy
+      if ev is not None:
+        ev.record()
+        used[0] = True
+
+    def out(*shape):
+      t = torch.empty(shape, dtype=torch.float32, device=dev)
+      if POISON_SCRATCH:  # (train_static.py) under test: every element must be written by the kernels
+        t.fill_(float('nan'))
+      return t
+
+    images, cameras = out(V, H, W, 3), out(V, 34)
+    st = stream_of(ints)
+    hp, dp = host.data_ptr(), ints.data_ptr()
+    call('dyn_scene_views', ctypes.byref(self._store), ctypes.c_void_p(hp), ctypes.c_void_p(dp), counts[0], counts[1], counts[2], _p(images),
+         _p(cameras), st)
+    px = dict(ray_o=out(R, 3), ray_d=out(R, 3), uv=out(R, 2), rgb=out(R, 3), disp=out(R), motion_mask=out(R), static_mask=out(R),
+              flows=out(6, R, 2), masks=out(6, R, 1), camera=out(1, 34), anchor_camera=out(1, 34))
+    p = params('DynSceneSupervisionParams', frame=int(frame), anchor_frame=int(anchor_frame), R=R,
+               sel_host=None if sel is None else ctypes.c_void_p(hp + 16 * V), sel=None if sel is None else ctypes.c_void_p(dp + 16 * V),
+               **{k: _p(v) for k, v in px.items()})
+    call('dyn_scene_supervision', ctypes.byref(self._store), ctypes.byref(p), st)
+    return images, cameras, px
+
+
+class _Null(object):
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *a):
+    return False
+
+
+class DeviceRaySampler(object):
+  """``RaySamplerSingleImage``'s contract (sample_ray.py) for one planned frame of a DeviceScene: ``.H``, ``.W``, ``.rgb``, ``.disp``, ``get_all()`` and
+  ``random_sample(N_rand, sample_mode, center_ratio)``, with the values of the host sampler on the collated item of the same plan."""
+
+  def __init__(self, scene, plan):
+    self.scene, self.plan = scene, plan
+    self.H, self.W = scene.H, scene.W
+    self.device = scene.device
+    self.render_stride = 1
+    self.depth_range = scene.depth_range
+    self._all = None
+
+  def _batch(self, sel):
+    pl, c = self.plan, self.plan['counts']
+    images, cameras, px = self.scene.assemble(pl['desc'], c, pl['idx'], pl['anchor_idx'], sel)
+    a, b = c[0], c[0] + c[1]
+    px.update(src_rgbs=images[None, :a], src_cameras=cameras[None, :a], anchor_src_rgbs=images[None, a:b], anchor_src_cameras=cameras[None, a:b],
+              static_src_rgbs=images[None, b:], static_src_cameras=cameras[None, b:])
+    return px
+
+  def get_all(self):
+    """All rays of the frame with the per-view tensors (``RaySamplerSingleImage.get_all``)."""
+    if self._all is None:
+      self._all = self._batch(None)
+    o = self._all
+    return {
+        'ray_o': o['ray_o'], 'ray_d': o['ray_d'], 'depth_range': self.depth_range, 'camera': o['camera'], 'render_camera': None,
+        'anchor_camera': o['anchor_camera'], 'rgb': o['rgb'], 'src_rgbs': o['src_rgbs'], 'src_cameras': o['src_cameras'],
+        'anchor_src_rgbs': o['anchor_src_rgbs'], 'anchor_src_cameras': o['anchor_src_cameras'], 'static_src_rgbs': o['static_src_rgbs'],
+        'static_src_cameras': o['static_src_cameras'], 'static_src_masks': None, 'disp': o['disp'][:, None].squeeze(),
+        'motion_mask': o['motion_mask'][:, None].squeeze(), 'static_mask': o['static_mask'][:, None].squeeze(), 'uv_grid': o['uv'],
+        'flows': o['flows'], 'masks': o['masks'],
+    }
+
+  @property
+  def rgb(self):
+    return self.get_all()['rgb']  # [H*W, 3]
+
+  @property
+  def disp(self):
+    return self.get_all()['disp'].reshape(-1, 1)  # [H*W, 1]
+
+  def sample_random_pixel(self, N_rand, sample_mode, center_ratio=0.8):
+    """``RaySamplerSingleImage.sample_random_pixel``: the same draws from ``sample_ray.rng``."""
+    if sample_mode == 'center':
+      border_H = int(self.H * (1 - center_ratio) / 2.0)
+      border_W = int(self.W * (1 - center_ratio) / 2.0)
+      u, v = np.meshgrid(np.arange(border_H, self.H - border_H), np.arange(border_W, self.W - border_W))
+      u = u.reshape(-1)
+      v = v.reshape(-1)
+      if N_rand > u.shape[0]:
+        raise ValueError(f'N_rand={N_rand} is larger than the pool of {u.shape[0]} centre pixels')
+      select_inds = sample_ray.rng.choice(u.shape[0], size=(N_rand,), replace=False)
+      select_inds = v[select_inds] + self.W * u[select_inds]
+    elif sample_mode == 'uniform':
+      if N_rand > self.H * self.W:
+        raise ValueError(f'N_rand={N_rand} is larger than the pool of {self.H * self.W} pixels')
+      select_inds = sample_ray.rng.choice(self.H * self.W, size=(N_rand,), replace=False)
+    else:
+      raise NotImplementedError
+    return select_inds
+
+  def random_sample(self, N_rand, sample_mode, center_ratio=0.8):
+    """Random pixel batch with its supervision (``RaySamplerSingleImage.random_sample``), assembled on the device."""
+    if N_rand < 1:
+      raise ValueError(f'N_rand={N_rand}')
+    select_inds = self.sample_random_pixel(N_rand, sample_mode, center_ratio)
+    o = self._batch(select_inds)
+    return {
+        'ray_o': o['ray_o'], 'ray_d': o['ray_d'], 'camera': o['camera'], 'anchor_camera': o['anchor_camera'], 'depth_range': self.depth_range,
+        'rgb': o['rgb'], 'disp': o['disp'][:, None].squeeze(), 'motion_mask': o['motion_mask'][:, None].squeeze(),
+        'static_mask': o['static_mask'][:, None].squeeze(), 'uv_grid': o['uv'], 'flows': o['flows'], 'masks': o['masks'],
+        'src_rgbs': o['src_rgbs'], 'src_cameras': o['src_cameras'], 'static_src_rgbs': o['static_src_rgbs'],
+        'static_src_cameras': o['static_src_cameras'], 'static_src_masks': None, 'anchor_src_rgbs': o['anchor_src_rgbs'],
+        'anchor_src_cameras': o['anchor_src_cameras'], 'selected_inds': select_inds,
+    }

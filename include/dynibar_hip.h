@@ -672,6 +672,64 @@ typedef struct {
 } DynFrameMetricsParams;
 int dyn_frame_metrics(const DynFrameMetricsParams* p, double* sums, void* stream);
 
+/* ====== training batches from a device-resident scene (ibrnet/data_loaders/monocular.py:120-144, :300-425; sample_ray.py:262-331) ==========
+ * The scene is uploaded once: frames and virtual views as uint8 images, every image padded to image_stride bytes (a multiple of 16, so
+ * that dword loads stay aligned when H*W*3 is not a multiple of 4), the optional source masks as uint8 in the same way, disparity and
+ * flows as fp32, the per-pixel masks as uint8 0 / 1.  A batch is then two launches:
+ *   dyn_scene_views        the three source-view lists (ref, anchor, static; V = V_ref + V_anchor + V_static views, consecutive in desc,
+ *                          images and cameras).  desc holds four int32 per view: image frame, virtual index (0..7) or -1, mask frame or -1,
+ *                          intrinsics frame.  The pose is poses[image frame], or vposes[image frame][virtual index] for a virtual view.
+ *                          images [V,H,W,3] = float(u8) / 255.0f, with a mask times float(m) / 255.0f (a one-channel mask applies to the
+ *                          pixel's three channels) -- IEEE divisions: numpy's astype(float32) / 255.0 and src_rgb * st_mask bit for bit.
+ *                          cameras [V,34] = [H, W, K(16), c2w(16)].
+ *   dyn_scene_supervision  for R pixel indices sel[r] (row-major, y * W + x) of one frame: ray_o / ray_d [R,3] with the bits dyn_image_rays
+ *                          gives those pixels, uv [R,2] = (x, y), rgb [R,3] by the same / 255.0f rule, and copies: disp [R], motion_mask
+ *                          [R], static_mask [R], flows [6,R,2], masks [6,R].  sel NULL: every pixel in order (R must be H*W).
+ *                          camera / anchor_camera [34] (each may be NULL): the cameras of frame and anchor_frame.
+ * Every output element is written.  Limits: H*W*3 < 2^31; at most 32 views per list (the network engine's own limit) and at least one
+ * in all; R >= 1.
+ * Argument checking happens on the host BEFORE anything is launched: desc_host / sel_host are host-readable copies of the DEVICE arrays
+ * desc / sel (the pinned staging buffer they were copied from), and a frame id, virtual index, mask frame or pixel index out of range, a
+ * list of more than 32 views, or a virtual view / mask asked of a store that has none returns DYN_E_INVALID with a message.  The kernels
+ * check the same indices again and write zeros for a bad one: they never read out of bounds. */
+typedef struct {
+  int N, H, W;                 /* frames, image size */
+  long image_stride;           /* bytes from one stored image to the next: >= H*W*3, a multiple of 16 */
+  const uint8_t* frames;       /* N images, 16-byte aligned */
+  const uint8_t* vviews;       /* N*8 images (frame-major), or NULL */
+  const uint8_t* src_masks;    /* N masks, or NULL */
+  int mask_channels;           /* 1: [H,W]; 3: [H,W,3] */
+  long mask_stride;            /* bytes from one mask to the next: >= H*W*mask_channels, a multiple of 16 */
+  const float* intrinsics;     /* [N,16] */
+  const float* poses;          /* [N,16] camera-to-world */
+  const float* vposes;         /* [N,8,16], or NULL */
+  const float* disp;           /* [N,H,W]      (the rest: dyn_scene_supervision only) */
+  const uint8_t* motion_mask;  /* [N,H,W] 0 / 1 */
+  const uint8_t* static_mask;  /* [N,H,W] 0 / 1 */
+  const float* flows;          /* [N,6,H,W,2], 8-byte aligned */
+  const uint8_t* flow_masks;   /* [N,6,H,W] 0 / 1 */
+} DynSceneStore;
+int dyn_scene_views(const DynSceneStore* s, const int32_t* desc_host, const int32_t* desc, int V_ref, int V_anchor, int V_static, float* images,
+                    float* cameras, void* stream);
+typedef struct {
+  int frame, anchor_frame;
+  int R;
+  const int32_t* sel_host;     /* HOST copy of sel, read by the argument check */
+  const int32_t* sel;          /* DEVICE [R], or NULL for all H*W pixels */
+  float* ray_o;
+  float* ray_d;
+  float* uv;
+  float* rgb;
+  float* disp;
+  float* motion_mask;
+  float* static_mask;
+  float* flows;                /* [6,R,2], 8-byte aligned */
+  float* masks;                /* [6,R] */
+  float* camera;               /* [34] or NULL */
+  float* anchor_camera;        /* [34] or NULL */
+} DynSceneSupervisionParams;
+int dyn_scene_supervision(const DynSceneStore* s, const DynSceneSupervisionParams* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

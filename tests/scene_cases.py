@@ -1,0 +1,322 @@
+"""Support for the device-scene tests (dynibar_amd/scene.py, csrc/dyn_scene.h): a seeded synthetic scene, fake random sources for the view
+selection, a numpy restatement of what ``MonocularDataset`` makes of the same arrays and plan (ibrnet/data_loaders/monocular.py:120-144 load_src_view,
+:300-425 the stacking and the returned item, then ``default_collate`` with batch size 1), and the checks the device and the emulator tests share.
+Test infrastructure: nothing in dynibar_amd imports this.
+
+The restatement reads no files: ``imageio.imread(f)`` is the scene's uint8 array of that frame, ``np.load(disp) / scale`` its ``disp``, the
+flows and masks its ``flows`` / ``flow_masks``; ``cv2.resize(..., INTER_NEAREST)`` of a mask to the image's own size is the identity."""
+import functools
+import types
+
+import numpy as np
+import torch
+
+N_FRAMES = 9
+
+
+def args_of(num_source_views=2, max_range=6, init_decay_epoch=10, num_vv=0, mask_src_view=False):
+  return types.SimpleNamespace(num_source_views=num_source_views, max_range=max_range, init_decay_epoch=init_decay_epoch, num_vv=num_vv,
+                               mask_src_view=mask_src_view)
+
+
+# ---- random sources ---------------------------------------------------------------------------------------------------------------
+class RecordingRng(object):
+  """np.random.RandomState(seed) that records every call (name, args, kwargs); ``idx`` forces the value of the first randint (the frame)."""
+
+  def __init__(self, seed, idx=None):
+    self.rs, self.calls, self.idx = np.random.RandomState(seed), [], idx
+
+  def randint(self, *a, **k):
+    self.calls.append(('randint', a, k))
+    v = self.rs.randint(*a, **k)
+    if len(self.calls) == 1 and self.idx is not None:
+      assert a[0] <= self.idx < a[1]
+      return self.idx
+    return v
+
+  def choice(self, *a, **k):
+    self.calls.append(('choice', a, k))
+    return self.rs.choice(*a, **k)
+
+
+# ---- poses of the get_nearest_pose_ids golden --------------------------------------------------------------------------------------
+GOLDEN_POSES = ('scattered', 'ties', 'float32', 'long')
+
+
+def golden_poses(name):
+  """[N, 4, 4] camera-to-world.  'ties': mirrored and duplicated positions on a lattice, so that many distances are EXACTLY equal and the
+  order of argsort's ties shows; 'float32': the dtype the distances are then computed in; 'long': 40 frames (several strides of 5)."""
+  rng = np.random.default_rng([{'scattered': 1, 'ties': 2, 'float32': 3, 'long': 4}[name], 77])
+  n = 40 if name == 'long' else 12
+  poses = np.tile(np.eye(4), (n, 1, 1))
+  if name == 'ties':
+    loc = rng.integers(-1, 2, (n, 3)).astype(np.float64)  # lattice points: exact distances, many equal
+    loc[n // 2:] = -loc[:n - n // 2]                      # mirrored about the origin
+    loc[3] = loc[0]                                       # a duplicated position
+    poses[:, :3, 3] = loc
+  else:
+    poses[:, :3, 3] = rng.uniform(-1.0, 1.0, (n, 3))
+  return poses.astype(np.float32) if name == 'float32' else poses
+
+
+# ---- the synthetic scene ----------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=16)
+def make_scene(H, W, mask_channels=0, N=N_FRAMES, seed=0):
+  """Seeded arrays as a loader would hold them once per scene (read-only: shared between tests).  Images and source masks use every byte value;
+  each frame has its own focal length, so a camera that took the intrinsics of the wrong frame differs."""
+  from dynibar_amd import synthetic as syn
+  rng = np.random.default_rng([seed, H, W, 5])
+  a = dict(H=H, W=W, N=N)
+  a['images'] = rng.integers(0, 256, (N, H, W, 3), dtype=np.uint8)
+  a['images'][:, 0, 0], a['images'][:, -1, -1] = (0, 255, 1), (254, 0, 255)
+  a['virtual_views'] = rng.integers(0, 256, (N, 8, H, W, 3), dtype=np.uint8)
+  intr = np.tile(np.eye(4), (N, 1, 1))
+  for i in range(N):
+    intr[i, 0, 0] = intr[i, 1, 1] = 0.78 * W * rng.uniform(0.95, 1.05)
+    intr[i, 0, 2], intr[i, 1, 2] = (W - 1) * 0.5, (H - 1) * 0.5
+  a['intrinsics'] = intr                                                       # float64, like batch_parse_llff_poses
+  a['poses'] = np.stack([syn.make_pose(rng, 0.4, 0.05) for _ in range(N)])
+  a['virtual_poses'] = np.stack([[syn.make_pose(rng, 0.4, 0.05) for _ in range(8)] for _ in range(N)])
+  a['depth_range'] = (np.float64(1.0) + rng.uniform(0, 0.1), np.float64(20.0) + rng.uniform(0, 0.1))
+  a['disp'] = (0.05 + 0.5 * rng.random((N, H, W))).astype(np.float32)
+  a['motion_mask'] = (rng.random((N, H, W)) < 0.5).astype(np.float32)
+  a['static_mask'] = rng.random((N, H, W)) < 0.3                               # bool
+  a['flows'] = (4.0 * rng.standard_normal((N, 6, H, W, 2))).astype(np.float32)
+  a['flow_masks'] = (rng.random((N, 6, H, W)) < 0.8).astype(np.uint8)
+  a['source_masks'] = None
+  if mask_channels:
+    a['source_masks'] = rng.integers(0, 256, (N, H, W) + ((3,) if mask_channels == 3 else ()), dtype=np.uint8)
+    a['source_masks'][:, 0, :2] = np.array([0, 255]).reshape((2,) + (1,) * (mask_channels == 3))
+  for v in a.values():
+    if isinstance(v, np.ndarray):
+      v.setflags(write=False)
+  return a
+
+
+_SCENES = {}
+
+
+def device_scene(device, H, W, mask_channels=0, N=N_FRAMES, seed=0):
+  """the DeviceScene of make_scene(...), uploaded once per test session and device"""
+  from dynibar_amd import scene
+  key = (str(device), H, W, mask_channels, N, seed)
+  if key not in _SCENES:
+    a = make_scene(H, W, mask_channels, N, seed)
+    _SCENES[key] = scene.DeviceScene(device, a['images'], a['intrinsics'], a['poses'], a['depth_range'], a['disp'], a['motion_mask'], a['static_mask'],
+                                     a['flows'], a['flow_masks'], a['virtual_views'], a['virtual_poses'], a['source_masks'])
+  return _SCENES[key]
+
+
+# ---- the reference's item from the same arrays and plan ---------------------------------------------------------------------------
+def load_src_view(img_u8, pose, intrinsics, st_mask_u8=None):
+  """monocular.py:120-144"""
+  src_rgb = img_u8.astype(np.float32) / 255.0
+  img_size = src_rgb.shape[:2]
+  src_camera = np.concatenate((list(img_size), intrinsics.flatten(), pose.flatten())).astype(np.float32)
+  if st_mask_u8 is not None:
+    st_mask = st_mask_u8.astype(np.float32) / 255.0
+    if len(st_mask.shape) == 2:
+      st_mask = st_mask[..., None]
+    src_rgb = src_rgb * st_mask
+  return src_rgb, src_camera
+
+
+def restate_item(a, plan, mask_src_view):
+  """monocular.py:146-166, :300-425 for the ids of ``plan`` -> the collated ``data`` dictionary (every array with a leading 1)"""
+  idx, anchor_idx = plan['idx'], plan['anchor_idx']
+  intrinsics = a['intrinsics'][idx]
+  rgb, camera = load_src_view(a['images'][idx], a['poses'][idx], intrinsics)
+  img_size = rgb.shape[:2]
+  anchor_camera = np.concatenate((list(img_size), a['intrinsics'][anchor_idx].flatten(), a['poses'][anchor_idx].flatten())).astype(np.float32)
+  src_rgbs, src_cameras = [], []
+  for near_id in plan['nearest_pose_ids']:
+    r, c = load_src_view(a['images'][near_id], a['poses'][near_id], a['intrinsics'][near_id])
+    src_rgbs.append(r); src_cameras.append(c)
+  for virtual_idx in plan['ref_virtual']:
+    r, c = load_src_view(a['virtual_views'][idx, virtual_idx], a['virtual_poses'][idx, virtual_idx], intrinsics)
+    src_rgbs.append(r); src_cameras.append(c)
+  static_src_rgbs, static_src_cameras = [], []
+  for st_near_id in plan['static_pose_ids']:
+    r, c = load_src_view(a['images'][st_near_id], a['poses'][st_near_id], a['intrinsics'][st_near_id],
+                         st_mask_u8=a['source_masks'][st_near_id] if mask_src_view else None)
+    static_src_rgbs.append(r); static_src_cameras.append(c)
+  anchor_src_rgbs, anchor_src_cameras = [], []
+  for near_id in plan['anchor_nearest_pose_ids']:
+    r, c = load_src_view(a['images'][near_id], a['poses'][near_id], a['intrinsics'][near_id])
+    anchor_src_rgbs.append(r); anchor_src_cameras.append(c)
+  for virtual_idx in plan['anchor_virtual']:
+    r, c = load_src_view(a['virtual_views'][anchor_idx, virtual_idx], a['virtual_poses'][anchor_idx, virtual_idx], intrinsics)  # (:385-389: idx's)
+    anchor_src_rgbs.append(r); anchor_src_cameras.append(c)
+  depth_range = torch.tensor([a['depth_range'][0] * 0.9, a['depth_range'][1] * 1.5]).float()
+  N = a['N']
+  item = {
+      'id': idx, 'anchor_id': anchor_idx, 'num_frames': N, 'ref_time': float(idx / float(N)), 'anchor_time': float(anchor_idx / float(N)),
+      'nearest_pose_ids': torch.from_numpy(np.array(plan['nearest_pose_ids'])),
+      'anchor_nearest_pose_ids': torch.from_numpy(np.array(plan['anchor_nearest_pose_ids'])),
+      'rgb': torch.from_numpy(rgb[..., 0:3]).float(), 'disp': torch.from_numpy(np.array(a['disp'][idx])).float(),
+      'motion_mask': torch.from_numpy(np.array(a['motion_mask'][idx], dtype=np.float32)).float(),
+      'static_mask': torch.from_numpy(np.array(a['static_mask'][idx], dtype=np.float32)).float(),
+      'flows': torch.from_numpy(np.array(a['flows'][idx])).float(), 'masks': torch.from_numpy(np.array(a['flow_masks'][idx], dtype=np.float32)).float(),
+      'camera': torch.from_numpy(camera).float(), 'anchor_camera': torch.from_numpy(anchor_camera).float(),
+      'src_rgbs': torch.from_numpy(np.stack(src_rgbs, axis=0)[..., :3]).float(), 'src_cameras': torch.from_numpy(np.stack(src_cameras, axis=0)).float(),
+      'static_src_rgbs': torch.from_numpy(np.stack(static_src_rgbs, axis=0)[..., :3]).float(),
+      'static_src_cameras': torch.from_numpy(np.stack(static_src_cameras, axis=0)).float(),
+      'anchor_src_rgbs': torch.from_numpy(np.stack(anchor_src_rgbs, axis=0)[..., :3]).float(),
+      'anchor_src_cameras': torch.from_numpy(np.stack(anchor_src_cameras, axis=0)).float(),
+      'depth_range': depth_range,
+  }
+  from torch.utils.data import default_collate
+  data = default_collate([item])
+  data['rgb_path'] = ['frame']
+  return data
+
+
+@functools.lru_cache(maxsize=64)
+def planned(H, W, mask_channels, num_vv, idx, seed=0, epoch=0):
+  """(plan, collated data of the restatement) for a forced target frame: computed once, shared, not modified"""
+  from dynibar_amd import scene as scene_mod
+  a = make_scene(H, W, mask_channels)
+  args = args_of(num_vv=num_vv, mask_src_view=bool(mask_channels))
+  host = types.SimpleNamespace(N=a['N'], poses_host=a['poses'], has_source_masks=bool(mask_channels))
+  host.descriptors = lambda *x: scene_mod.DeviceScene.descriptors(host, *x)
+  plan = scene_mod.DeviceScene.plan(host, epoch, args, RecordingRng(seed, idx=idx))  # the plan is host work: no device scene needed
+  return plan, restate_item(a, plan, bool(mask_channels))
+
+
+# ---- comparisons -------------------------------------------------------------------------------------------------------------------
+def assert_same_batch(got, want, what):
+  """same key set, and per key: None alike, selected_inds equal arrays, tensors of the same shape, dtype and device type with the same bits"""
+  import parity
+  assert set(got.keys()) == set(want.keys()), f'{what}: keys differ: {sorted(set(got) ^ set(want))}'
+  for k, w in want.items():
+    g = got[k]
+    if w is None:
+      assert g is None, f'{what}: {k} must be None'
+    elif k == 'selected_inds':
+      assert isinstance(g, np.ndarray) and g.dtype == w.dtype and np.array_equal(g, w), f'{what}: selected_inds differ'
+    else:
+      assert tuple(g.shape) == tuple(w.shape) and g.dtype == w.dtype and g.device.type == w.device.type, \
+          f'{what}: {k} is {g.dtype} {tuple(g.shape)} on {g.device}, the host path gives {w.dtype} {tuple(w.shape)} on {w.device}'
+      parity.assert_bitexact(g, w, f'{what}: {k}')
+      if g.dtype == torch.float32:  # (torch.equal takes -0.0 for 0.0)
+        assert torch.equal(g.contiguous().view(torch.int32).cpu(), w.contiguous().view(torch.int32).cpu()), f'{what}: {k} differs in a sign of zero'
+
+
+def pool_size(H, W, mode, center_ratio=0.8):
+  if mode == 'uniform':
+    return H * W
+  bh, bw = int(H * (1 - center_ratio) / 2.0), int(W * (1 - center_ratio) / 2.0)
+  return (H - 2 * bh) * (W - 2 * bw)
+
+
+def both_samplers(device, H, W, mask_channels, num_vv, idx):
+  from dynibar_amd import sample_ray
+  plan, data = planned(H, W, mask_channels, num_vv, idx)
+  return device_scene(device, H, W, mask_channels).sampler(plan), sample_ray.RaySamplerSingleImage(data, device)
+
+
+def check_bit_equality(device, H, W, mask_channels, num_vv, N_rand, mode, seed=11):
+  """random_sample of the device sampler against the host sampler on the restated item, for the target frames at both ends (3 and N - 4).
+  N_rand beyond the pool of the mode (centre pixels of a larger image): both samplers refuse with ValueError, and the whole pool is compared."""
+  from dynibar_amd import sample_ray
+  for idx in (3, N_FRAMES - 4):
+    tag = f'scene batch [{H}x{W} masks={mask_channels} vv={num_vv} N_rand={N_rand} {mode} idx={idx}]'
+    dev_s, host_s = both_samplers(device, H, W, mask_channels, num_vv, idx)
+    n = N_rand
+    if n > pool_size(H, W, mode):
+      for s in (dev_s, host_s):
+        try:
+          s.random_sample(n, mode)
+        except ValueError:
+          pass
+        else:
+          raise AssertionError(f'{tag}: N_rand larger than the pool must raise ValueError')
+      n = pool_size(H, W, mode)
+    sample_ray.rng.seed(seed)
+    want = host_s.random_sample(n, mode)
+    sample_ray.rng.seed(seed)
+    got = dev_s.random_sample(n, mode)
+    assert_same_batch(got, want, tag)
+    if n == H * W:
+      assert 0 in got['selected_inds'] and H * W - 1 in got['selected_inds'], f'{tag}: the selection must hold the first and the last pixel'
+    for k, v in got.items():
+      if isinstance(v, torch.Tensor):
+        assert bool(torch.isfinite(v).all()), f'{tag}: {k} has elements the kernels did not write'
+
+
+def check_get_all(device, H, W, mask_channels, num_vv):
+  import parity
+  for idx in (3, N_FRAMES - 4):
+    tag = f'scene get_all [{H}x{W} masks={mask_channels} vv={num_vv} idx={idx}]'
+    dev_s, host_s = both_samplers(device, H, W, mask_channels, num_vv, idx)
+    assert (dev_s.H, dev_s.W) == (host_s.H, host_s.W) == (H, W)
+    got, want = dev_s.get_all(), host_s.get_all()
+    assert_same_batch(got, want, tag)
+    parity.assert_bitexact(dev_s.rgb, host_s.rgb.to(device), tag + ': .rgb')
+    parity.assert_bitexact(dev_s.disp, host_s.disp.to(device), tag + ': .disp')
+    assert tuple(dev_s.rgb.shape) == (H * W, 3) and tuple(dev_s.disp.shape) == (H * W, 1)
+
+
+def with_static_ids(scene, a, plan, static_ids, mask_src_view):
+  """the plan with another static list (the view selection itself never repeats a frame; a caller's own list may)"""
+  p = dict(plan)
+  p['static_pose_ids'] = np.asarray(static_ids)
+  p['desc'], p['counts'] = scene.descriptors(plan['idx'], plan['anchor_idx'], plan['nearest_pose_ids'], plan['anchor_nearest_pose_ids'],
+                                             p['static_pose_ids'], plan['ref_virtual'], plan['anchor_virtual'], mask_src_view)
+  return p, restate_item(a, p, mask_src_view)
+
+
+def check_repeated_and_many_views(device, H=17, W=19, mask_channels=1):
+  """a static list that repeats a frame; a list of exactly 32 views passes and every element is written; 33 views raise"""
+  from dynibar_amd import sample_ray
+  a, scene = make_scene(H, W, mask_channels), device_scene(device, H, W, mask_channels)
+  plan, _ = planned(H, W, mask_channels, 3, 3)
+  for ids in ([0, 2, 2, 7], [(5 * i + i // 8) % N_FRAMES for i in range(32)]):
+    p, data = with_static_ids(scene, a, plan, ids, True)
+    sample_ray.rng.seed(5)
+    want = sample_ray.RaySamplerSingleImage(data, device).random_sample(13, 'uniform')
+    sample_ray.rng.seed(5)
+    got = scene.sampler(p).random_sample(13, 'uniform')
+    assert_same_batch(got, want, f'scene batch, static list of {len(ids)} views')
+    assert got['static_src_rgbs'].shape[1] == len(ids) and bool(torch.isfinite(got['static_src_rgbs']).all())
+  for call in (lambda: with_static_ids(scene, a, plan, list(range(9)) * 3 + list(range(6)), True),
+               lambda: scene.assemble(np.zeros((33 + 2, 4), np.int32), (1, 1, 33), 3, 4, None)):
+    try:
+      call()
+    except ValueError as e:
+      assert '32' in str(e)
+    else:
+      raise AssertionError('a list of 33 views must raise ValueError')
+
+
+def check_bad_indices(device, H=17, W=19):
+  """a frame id, a virtual index, a mask frame or a pixel index out of range is refused on the host, by the library's own check (the message
+  comes through dyn_last_error) -- nothing is launched -- and a valid call afterwards still gives the right bits"""
+  from dynibar_amd import _lib, sample_ray
+  scene = device_scene(device, H, W, 1)
+  plan, data = planned(H, W, 1, 3, 3)
+  good = plan['desc']
+
+  def refused(desc, sel, frame=3, anchor=4, match=''):
+    try:
+      scene.assemble(desc, plan['counts'], frame, anchor, sel)
+    except (ValueError, RuntimeError) as e:
+      assert match in str(e), f'{e!s} does not say {match!r}'
+      assert match.encode() in _lib.lib().dyn_last_error(), _lib.lib().dyn_last_error()
+    else:
+      raise AssertionError(f'a call with {match} out of range must be refused')
+
+  sel = np.arange(5)
+  for row, col, value, match in ((0, 0, N_FRAMES, 'image frame'), (1, 0, -1, 'image frame'), (6, 1, 8, 'virtual index'), (6, 1, -2, 'virtual index'),
+                                 (len(good) - 1, 2, N_FRAMES, 'mask frame'), (2, 3, N_FRAMES + 5, 'intrinsics frame')):
+    bad = good.copy()
+    bad[row, col] = value
+    refused(bad, sel, match=match)
+  refused(good, np.array([0, H * W]), match='pixel index')
+  refused(good, np.array([3, -1, 2]), match='pixel index')
+  refused(good, sel, frame=N_FRAMES, match='frame')
+  refused(good, sel, anchor=-1, match='anchor frame')
+  sample_ray.rng.seed(3)
+  want = sample_ray.RaySamplerSingleImage(data, device).random_sample(13, 'uniform')
+  sample_ray.rng.seed(3)
+  assert_same_batch(scene.sampler(plan).random_sample(13, 'uniform'), want, 'scene batch after refused calls')

@@ -1,0 +1,260 @@
+"""Training batches from a device-resident scene on the MI355X (dynibar_amd/scene.py, csrc/dyn_scene.h) against the existing host path:
+``scene.sampler(plan).random_sample(...)`` / ``get_all()`` and ``RaySamplerSingleImage(data, dev)`` on the collated item that
+tests/scene_cases.py restates from the same arrays and plan give the same keys, shapes, dtypes and bits; every output element is written
+(the outputs start as NaN under the suite: DYNIBAR_TRAIN_POISON, tests/conftest.py); bad indices are refused before a launch; the bits do not
+depend on the call or the stream; a batch costs one asynchronous copy and no synchronisation; and a training step fed from the device sampler
+gives the losses of one fed from the host sampler.  Shapes: (17, 19) and (5, 7) make H*W no multiple of 4 and H*W*3 odd (scalar tail, images
+that do not start on 16 bytes in the output), (16, 16) and (18, 32) take the float4 stores; (18, 32) with 30+ views is more than one workgroup
+per view and several views."""
+import types
+import warnings
+
+import numpy as np
+import pytest
+import torch
+import torch.utils._python_dispatch
+import torch.utils._pytree
+
+import scene_cases as sc
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+SHAPES = [(16, 16), (17, 19), (5, 7), (18, 32)]
+
+
+def _n_rand(H, W, which):
+  return {'one': 1, 'thirteen': 13, 'all': H * W}[which]
+
+
+@pytest.mark.parametrize('H,W', SHAPES)
+@pytest.mark.parametrize('mask_channels', [0, 1, 3])
+@pytest.mark.parametrize('num_vv', [0, 3])
+@pytest.mark.parametrize('n_rand', ['one', 'thirteen', 'all'])
+@pytest.mark.parametrize('mode', ['uniform', 'center'])
+def test_bit_equality_with_the_host_path(H, W, mask_channels, num_vv, n_rand, mode):
+  """check 1: random_sample key by key, target frames at both ends (idx = 3 and idx = N - 4); N_rand = H*W in uniform mode selects every pixel,
+  the first and the last included.  In centre mode H*W exceeds the pool of the larger images: both samplers refuse, the whole pool is compared."""
+  from dynibar_amd.train_static import POISON_SCRATCH
+  assert POISON_SCRATCH
+  sc.check_bit_equality(DEV, H, W, mask_channels, num_vv, _n_rand(H, W, n_rand), mode)
+
+
+@pytest.mark.parametrize('H,W', SHAPES)
+@pytest.mark.parametrize('mask_channels', [0, 1, 3])
+@pytest.mark.parametrize('num_vv', [0, 3])
+def test_get_all_equals_the_host_samplers(H, W, mask_channels, num_vv):
+  sc.check_get_all(DEV, H, W, mask_channels, num_vv)
+
+
+def test_stores_are_complete_repeated_frames_and_view_limits():
+  """check 2: NaN-filled outputs come back finite and equal to the restatement, with a static list that repeats a frame and with one of
+  exactly 32 views; 33 views raise"""
+  sc.check_repeated_and_many_views(DEV)
+
+
+def test_bad_indices_never_reach_a_kernel():
+  """check 3"""
+  sc.check_bad_indices(DEV)
+  torch.cuda.synchronize()
+
+
+def test_bitwise_determinism_across_calls_and_streams():
+  """check 4: two calls, a call on a side stream, and a call while other batches assemble on a second stream"""
+  from dynibar_amd import sample_ray
+  H, W = 18, 32
+  scene = sc.device_scene(DEV, H, W, 3)
+  plan, _ = sc.planned(H, W, 3, 3, 3)
+  other_plan, _ = sc.planned(H, W, 3, 3, sc.N_FRAMES - 4)
+
+  def run(p=plan, seed=7):
+    sample_ray.rng.seed(seed)
+    return scene.sampler(p).random_sample(64, 'uniform')
+
+  first = run()
+  second = run()
+  torch.cuda.synchronize()
+  side, busy = torch.cuda.Stream(), torch.cuda.Stream()
+  with torch.cuda.stream(side):
+    third = run()
+  torch.cuda.synchronize()
+  with torch.cuda.stream(busy):
+    for k in range(8):
+      run(other_plan, 20 + k)
+  fourth = run()
+  with torch.cuda.stream(busy):
+    for k in range(8):
+      run(other_plan, 30 + k)
+  torch.cuda.synchronize()
+  for tag, o in (('second call', second), ('side stream', third), ('beside other batches', fourth)):
+    sc.assert_same_batch(o, first, f'scene batch, {tag}')
+
+
+def test_one_copy_and_no_synchronisation():
+  """check 5: after a warm-up call (library load, the pinned staging buffers, allocator growth) a batch raises nothing under torch's sync debug
+  mode 'error' -- the one host-to-device copy is asynchronous from pinned memory -- and warns nothing under 'warn'"""
+  from dynibar_amd import sample_ray
+  H, W = 18, 32
+  scene = sc.device_scene(DEV, H, W, 1)
+  plan, data = sc.planned(H, W, 1, 3, 3)
+  sample_ray.rng.seed(2)
+  want = sample_ray.RaySamplerSingleImage(data, DEV).random_sample(64, 'center')
+  sample_ray.rng.seed(2)
+  scene.sampler(plan).random_sample(64, 'center')
+  torch.cuda.synchronize()
+  sample_ray.rng.seed(2)
+  torch.cuda.set_sync_debug_mode('error')
+  try:
+    got = scene.sampler(plan).random_sample(64, 'center')
+  finally:
+    torch.cuda.set_sync_debug_mode('default')
+  sc.assert_same_batch(got, want, 'scene batch under sync debug mode')
+  torch.cuda.set_sync_debug_mode('warn')
+  try:
+    with warnings.catch_warnings(record=True) as seen:
+      warnings.simplefilter('always')
+      for _ in range(6):  # (more batches than staging slots: a slot is reused without a wait)
+        scene.sampler(plan).random_sample(64, 'center')
+  finally:
+    torch.cuda.set_sync_debug_mode('default')
+  syncs = [w for w in seen if 'synchroniz' in str(w.message).lower()]
+  print('  synchronising calls of six batches:', [(w.filename, w.lineno) for w in syncs])
+  assert len(syncs) == 0, [(str(w.message), w.filename, w.lineno) for w in seen]
+
+
+class _Copies(torch.utils._python_dispatch.TorchDispatchMode):
+  """every aten call that moves tensor data between the host and a device: an operator with a host tensor among its inputs and a device tensor
+  among its outputs (copy_ returns its destination) is a host-to-device copy; a device input with a host output, or a scalar read of a device
+  tensor (.item(), .tolist()), a device-to-host copy"""
+
+  def __init__(self):
+    super().__init__()
+    self.h2d, self.d2h = [], []
+
+  def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+    out = func(*args, **(kwargs or {}))
+    flat = torch.utils._pytree.tree_flatten
+    ins = [t for t in flat((args, kwargs or {}))[0] if isinstance(t, torch.Tensor)]
+    outs = [t for t in flat(out)[0] if isinstance(t, torch.Tensor)]
+    on_dev = lambda ts: any(t.device.type == 'cuda' for t in ts)
+    on_host = lambda ts: any(t.device.type == 'cpu' for t in ts)
+    if on_host(ins) and on_dev(outs):
+      self.h2d.append((str(func), [t.numel() * t.element_size() for t in ins if t.device.type == 'cpu']))
+    if on_dev(ins) and (on_host(outs) or 'local_scalar' in str(func)):
+      self.d2h.append(str(func))
+    return out
+
+
+def test_one_host_to_device_copy_and_none_back():
+  """check 5, the copies: torch moves data for a batch exactly once, 4 (4 V + N_rand) bytes from the pinned staging buffer to the device, and
+  nothing from the device to the host (the library itself copies nothing: dyn_scene.h has no memcpy).  The host sampler, counted the same way
+  for comparison, makes about twenty."""
+  from dynibar_amd import sample_ray
+  H, W, n_rand = 18, 32, 64
+  scene = sc.device_scene(DEV, H, W, 1)
+  plan, data = sc.planned(H, W, 1, 3, 3)
+  scene.sampler(plan).random_sample(n_rand, 'uniform')  # warm-up
+  torch.cuda.synchronize()
+  with _Copies() as seen:
+    batch = scene.sampler(plan).random_sample(n_rand, 'uniform')
+  V = sum(plan['counts'])
+  print('  device sampler: host-to-device', seen.h2d, 'device-to-host', seen.d2h)
+  assert len(seen.h2d) == 1 and seen.h2d[0][0].startswith('aten.copy_') and seen.h2d[0][1] == [4 * (4 * V + n_rand)], seen.h2d
+  assert seen.d2h == [], seen.d2h
+  assert batch['src_rgbs'].is_cuda and isinstance(batch['selected_inds'], np.ndarray)
+  with _Copies() as host_seen:
+    sample_ray.RaySamplerSingleImage(data, DEV).random_sample(n_rand, 'uniform')
+  print(f'  host sampler: {len(host_seen.h2d)} host-to-device copies, {len(host_seen.d2h)} device-to-host')
+  assert len(host_seen.h2d) >= 15  # (the counter sees the copies of the path this one replaces)
+
+
+# ---- check 6: it trains ------------------------------------------------------------------------------------------------------------
+def _dct_basis(K, T):
+  b = np.zeros((T, K), np.float32)
+  for t in range(T):
+    for k in range(1, K + 1):
+      b[t, k - 1] = np.sqrt(2.0 / T) * np.cos(np.pi / (2.0 * T) * (2 * t + 1) * k)
+  return torch.from_numpy(b)
+
+
+def _two_steps(sampler_of, num_vv, S=32, R=64):
+  """One static-bootstrap step (train.py:120-199) and one main-loop step (:234-467) on fresh seeded weights, fed by ``sampler_of() ->
+  (train_data, ray_sampler)``.  -> ({stage: loss}, {stage: {leaf: gradient}})"""
+  import cases
+  import objective_cases as oc
+  from dynibar_amd import criterion, objective, projection, render_ray, sample_ray, synthetic as syn, train_encoder
+  P = lambda kind, **kw: {k: torch.from_numpy(v).to(DEV).requires_grad_(True) for k, v in syn.make_weights(kind, 0, **kw).items() if k != 's'}
+  model = types.SimpleNamespace(net_coarse_st=P('static'), net_coarse_dy=P('dynamic'), motion_mlp=P('motion', num_basis=cases.NUM_BASIS),
+                                trajectory_basis=_dct_basis(cases.NUM_BASIS, cases.NUM_FRAMES).to(DEV).requires_grad_(True))
+  enc = [{k: torch.from_numpy(v).to(DEV).requires_grad_(True) for k, v in syn.make_encoder_weights(sd).items() if k in train_encoder.PARAMS}
+         for sd in (0, 1)]
+  leaves = {'trajectory_basis': model.trajectory_basis}
+  for n in ('net_coarse_st', 'net_coarse_dy', 'motion_mlp'):
+    leaves.update({f'{n}.{k}': v for k, v in getattr(model, n).items()})
+  for i, e in enumerate(enc):
+    leaves.update({f'feature_net{i}.{k}': v for k, v in e.items()})
+  args = oc.args_of(anti_alias_pooling=0, mask_rgb=1, occ_weights_mode=0, num_vv=num_vv)
+  projector, obj = projection.Projector(DEV), objective.MonoObjective(args)
+  losses, grads = {}, {}
+  for stage, seed in (('bootstrap', 41), ('main', 42)):
+    for v in leaves.values():
+      v.grad = None
+    train_data, ray_sampler = sampler_of()
+    ref_t, anchor_t = train_data['ref_time'].to(DEV), train_data['anchor_time'].to(DEV)
+    nearest, anchor_nearest = train_data['nearest_pose_ids'].squeeze().tolist(), train_data['anchor_nearest_pose_ids'].squeeze().tolist()
+    ref_idx, anchor_idx = int(train_data['id'].item()), int(train_data['anchor_id'].item())
+    ref_off, anchor_off = [int(i - ref_idx) for i in nearest], [int(i - anchor_idx) for i in anchor_nearest]
+    num_dy_views = len(ref_off) + num_vv
+    sample_ray.rng.seed(seed)
+    ray_batch = ray_sampler.random_sample(R, sample_mode='uniform')
+    cb = torch.cat([ray_batch['src_rgbs'].squeeze(0).permute(0, 3, 1, 2), ray_batch['anchor_src_rgbs'].squeeze(0).permute(0, 3, 1, 2)], dim=0)
+    cb_maps, _ = train_encoder.encoder_forward(enc[0], cb)
+    st_maps, _ = train_encoder.encoder_forward(enc[1], ray_batch['static_src_rgbs'].squeeze(0).permute(0, 3, 1, 2))
+    ret = render_ray.render_rays_mono((ref_idx, anchor_idx), (ref_t, anchor_t), (ref_off, anchor_off), ray_batch, model,
+                                      (cb_maps[0:num_dy_views], cb_maps[num_dy_views:], st_maps), projector, S, args, inv_uniform=True, det=True,
+                                      is_train=(stage == 'main'), num_vv=num_vv)
+    if stage == 'bootstrap':
+      w = (1.0 - ray_batch['static_mask'].float()) * ret['outputs_coarse_ref']['mask'].float()
+      loss = criterion.compute_rgb_loss(ret['outputs_coarse_st']['rgb'], ray_batch, w)
+    else:
+      loss, _ = obj(ret, ray_batch, 0)
+    loss.backward()
+    losses[stage] = loss.detach().clone()
+    grads[stage] = {k: v.grad.detach().clone() for k, v in leaves.items() if v.grad is not None}
+  return losses, grads
+
+
+def _spread(a, b):
+  """the largest difference of two runs' gradients, per leaf relative to the leaf's largest gradient"""
+  worst = 0.0
+  for stage in a:
+    assert set(a[stage]) == set(b[stage])
+    for k, g in a[stage].items():
+      scale = float(g.abs().max())
+      if scale > 0:
+        worst = max(worst, float((g - b[stage][k]).abs().max()) / scale)
+      else:
+        assert float(b[stage][k].abs().max()) == 0.0, k
+  return worst
+
+
+def test_it_trains():
+  """check 6: an 18 x 32 scene of 9 frames, 64 rays: one bootstrap and one main-loop step fed from the device sampler and from the host sampler
+  with the same plan and seeds.  The batches are bit-identical, so the losses agree bit for bit.  The gradients are summed with fp32 atomics,
+  so two runs do not agree bit for bit: the device-fed run is held to twice the spread two host-fed runs show between themselves."""
+  from dynibar_amd import sample_ray
+  H, W, num_vv = 18, 32, 3
+  scene = sc.device_scene(DEV, H, W, 1)
+  plan, data = sc.planned(H, W, 1, num_vv, 4)
+  device_fed = lambda: (plan['train_data'], scene.sampler(plan))
+  host_fed = lambda: (data, sample_ray.RaySamplerSingleImage(data, DEV))
+  loss_h, grad_h = _two_steps(host_fed, num_vv)
+  loss_h2, grad_h2 = _two_steps(host_fed, num_vv)
+  loss_d, grad_d = _two_steps(device_fed, num_vv)
+  for stage in ('bootstrap', 'main'):
+    print(f'  {stage}: loss {float(loss_d[stage]):.9g} (device-fed) {float(loss_h[stage]):.9g} (host-fed), {len(grad_d[stage])} gradient tensors')
+    assert bool(torch.isfinite(loss_d[stage])) and float(loss_d[stage]) > 0
+    assert torch.equal(loss_d[stage], loss_h[stage]) and torch.equal(loss_h2[stage], loss_h[stage]), f'{stage}: the losses differ'
+    assert len(grad_d[stage]) > 20 and all(bool(torch.isfinite(g).all()) for g in grad_d[stage].values())
+  host_spread, device_diff = _spread(grad_h, grad_h2), _spread(grad_h, grad_d)
+  print(f'  gradients: two host-fed runs differ by {host_spread:.3e} of a leaf\'s largest gradient, device-fed against host-fed by {device_diff:.3e}')
+  assert device_diff <= 2.0 * host_spread, (device_diff, host_spread)

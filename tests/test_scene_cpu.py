@@ -1,0 +1,179 @@
+"""The host side of the device-resident scene (dynibar_amd/scene.py): the view selection draws from its random source exactly as
+MonocularDataset.__getitem__ does (monocular.py:146-298, :313, :375), its static ordering equals the real reference's get_nearest_pose_ids
+(tests/golden/scene_plan.npz, recorded by tests/golden/make_scene_golden.py), the plan's properties over 200 seeds, and the ValueErrors that
+need no device."""
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import scene_cases as sc
+from dynibar_amd import scene as scene_mod
+
+
+def _host_scene(N=sc.N_FRAMES, poses=None, masks=False, seed=0):
+  """what plan() reads of a DeviceScene (the selection is host work: no device, no library)"""
+  if poses is None:
+    rng = np.random.default_rng([seed, 3])
+    poses = np.tile(np.eye(4), (N, 1, 1))
+    poses[:, :3, 3] = rng.uniform(-1, 1, (N, 3))
+  s = types.SimpleNamespace(N=N, poses_host=poses, has_source_masks=masks)
+  s.descriptors = lambda *a: scene_mod.DeviceScene.descriptors(s, *a)
+  s.plan = lambda epoch, args, rng=np.random: scene_mod.DeviceScene.plan(s, epoch, args, rng)
+  return s
+
+
+@pytest.mark.parametrize('num_vv', [0, 2, 3])
+@pytest.mark.parametrize('epoch', [0, 9, 10, 25, 400])
+def test_draw_order(num_vv, epoch):
+  """names, arguments and count of the draws, in the reference's order; epochs on both sides of init_decay_epoch = 10 (max_step 1, 2, 3)"""
+  N, nsv, max_range = 30, 3, 12
+  args = sc.args_of(num_source_views=nsv, max_range=max_range, init_decay_epoch=10, num_vv=num_vv)
+  rng = sc.RecordingRng(epoch + 100 * num_vv)
+  plan = _host_scene(N).plan(epoch, args, rng)
+  max_step = min(3, epoch // 10 + 1)
+  max_interval = max_range // nsv
+  calls = rng.calls
+  assert calls[0] == ('randint', (3, N - 3), {})
+  assert calls[1] == ('choice', (2 * max_step,), {})
+  assert calls[2][0] == 'choice' and calls[2][1] == ([0, 1],) and list(calls[2][2]) == ['p'] and calls[2][2]['p'] == [1.0 - 0.005, 0.005]
+  assert calls[3] == ('randint', (max(2, max_interval - 2), max_interval + 1), {})
+  draws = calls[4:4 + 2 * nsv]
+  assert len(draws) == 2 * nsv and all(c[0] == 'randint' and c[2] == {} and c[1][0] == 1 for c in draws)
+  interval = draws[0][1][1] - 1
+  assert max(2, max_interval - 2) <= interval <= max_interval and all(c[1] == (1, interval + 1) for c in draws)
+  for c in calls[4 + 2 * nsv:]:
+    assert c == ('choice', (list(range(0, 8)),), {'size': num_vv, 'replace': False})
+  assert len(calls) == 4 + 2 * nsv + 2
+  assert len(plan['ref_virtual']) == len(plan['anchor_virtual']) == num_vv
+  assert abs(plan['anchor_idx'] - plan['idx']) <= max_step
+
+
+def test_nearest_pose_ids_equal_the_reference(golden_dir):
+  g = np.load(os.path.join(golden_dir, 'scene_plan.npz'))
+  assert sorted(g['names'].tolist()) == sorted(sc.GOLDEN_POSES)
+  for name in sc.GOLDEN_POSES:
+    poses = sc.golden_poses(name)
+    assert poses.dtype == g[f'{name}/poses'].dtype and np.array_equal(poses, g[f'{name}/poses']), f'{name}: the generator drifted from the golden'
+    for t in range(len(poses)):
+      got = scene_mod.nearest_pose_ids_dist(poses[t], poses, t)
+      assert got.dtype == g[f'{name}/ids'].dtype and np.array_equal(got, g[f'{name}/ids'][t]), f'{name}: target {t}'
+      assert got[-1] == t  # tar_id is sent to the end (its distance becomes 1e3)
+  ties = g['ties/poses'][:, :3, 3]
+  d = np.linalg.norm(ties[0] - ties, axis=1)
+  assert len(np.unique(d)) < len(d) - 2, 'the tie case must hold equal distances'
+
+
+def test_stride_5_fill_uses_the_nearest_ordering():
+  """a scene too short for the interval draws: the static list is filled from every fifth entry of the distance ordering"""
+  poses = sc.golden_poses('long')
+  s = _host_scene(len(poses), poses=poses)
+  args = sc.args_of(num_source_views=4, max_range=8)  # interval 2: at most 8 frames around idx; most seeds drop some, the fill adds them
+  filled = 0
+  for seed in range(40):
+    rng = sc.RecordingRng(seed, idx=3)  # at the scene's start: the draws below frame 0 are dropped
+    plan = s.plan(0, args, rng)
+    order = scene_mod.nearest_pose_ids_dist(poses[3], poses, 3)[::5]
+    interval = rng.calls[3 + 1][1][1] - 1
+    drawn = [3 + interval * ii + int(j) for ii, j in zip(range(-4, 4), _replay_rand_j(seed, rng))]
+    drawn = [i for i in drawn if 0 <= i < len(poses) and i != 3]
+    want = list(drawn)
+    for i in order:
+      if len(want) >= 8:
+        break
+      if i not in set(drawn):
+        want.append(i)
+    assert list(plan['static_pose_ids']) == sorted(want)
+    filled += len(want) > len(drawn)
+  assert filled > 0
+
+
+def _replay_rand_j(seed, rec):
+  """the rand_j draws of a recorded plan, replayed from the same seed"""
+  rs = np.random.RandomState(seed)
+  out = []
+  for name, a, k in rec.calls:
+    v = getattr(rs, name)(*a, **k)
+    if name == 'randint' and a[0] == 1:
+      out.append(v)
+  return out
+
+
+def test_plan_properties_over_200_seeds():
+  N, nsv = 30, 3
+  s = _host_scene(N, masks=True)
+  added = 0
+  for seed in range(200):
+    num_vv = seed % 4
+    args = sc.args_of(num_source_views=nsv, max_range=12, init_decay_epoch=10, num_vv=num_vv, mask_src_view=bool(seed % 2))
+    rng = sc.RecordingRng(seed)
+    plan = s.plan(seed % 40, args, rng)
+    idx, anchor = plan['idx'], plan['anchor_idx']
+    coin = np.random.RandomState(seed)
+    for name, a, k in rng.calls[:2]:
+      getattr(coin, name)(*a, **k)
+    add_idx = bool(coin.choice([0, 1], p=[1.0 - 0.005, 0.005]))
+    added += add_idx
+    assert 3 <= idx < N - 3 and 0 <= anchor < N and anchor != idx
+    assert plan['nearest_pose_ids'] == [idx + o for o in (1, 2, 3, -1, -2, -3)]
+    an, st = list(plan['anchor_nearest_pose_ids']), list(plan['static_pose_ids'])
+    assert all(0 <= i < N for i in an + st)
+    assert idx not in st
+    assert an == sorted(an) and (idx in an) == add_idx
+    assert set(an) - {idx} == {anchor + o for o in range(-3, 4) if 0 <= anchor + o < N and anchor + o != idx}
+    assert st == sorted(st) and 1 <= len(st) <= 2 * nsv
+    for vv in (plan['ref_virtual'], plan['anchor_virtual']):
+      assert len(vv) == num_vv == len(set(int(v) for v in vv)) and all(0 <= v < 8 for v in vv)
+    desc, (nr, na, ns) = plan['desc'], plan['counts']
+    assert desc.dtype == np.int32 and desc.shape == (nr + na + ns, 4) and (nr, na, ns) == (6 + num_vv, len(an) + num_vv, len(st))
+    assert desc[:6].tolist() == [[i, -1, -1, i] for i in plan['nearest_pose_ids']]
+    assert desc[6:nr].tolist() == [[idx, int(v), -1, idx] for v in plan['ref_virtual']]
+    assert desc[nr:nr + len(an)].tolist() == [[i, -1, -1, i] for i in an]
+    # the reference's quirk: the anchor's virtual views are images and poses of the anchor with the intrinsics of idx (monocular.py:385-389)
+    assert desc[nr + len(an):nr + na].tolist() == [[anchor, int(v), -1, idx] for v in plan['anchor_virtual']]
+    assert desc[nr + na:].tolist() == [[i, -1, i if args.mask_src_view else -1, i] for i in st]
+    td = plan['train_data']
+    assert set(td) == {'id', 'anchor_id', 'ref_time', 'anchor_time', 'nearest_pose_ids', 'anchor_nearest_pose_ids', 'num_frames'}
+    assert td['id'].dtype == torch.int64 and td['id'].tolist() == [idx] and td['anchor_id'].tolist() == [anchor] and td['num_frames'].tolist() == [N]
+    assert td['ref_time'].dtype == torch.float64 and td['ref_time'].tolist() == [idx / float(N)] and td['anchor_time'].tolist() == [anchor / float(N)]
+    assert td['nearest_pose_ids'].dtype == torch.int64 and td['nearest_pose_ids'].tolist() == [plan['nearest_pose_ids']]
+    assert td['anchor_nearest_pose_ids'].dtype == torch.int64 and td['anchor_nearest_pose_ids'].tolist() == [an]
+
+
+def test_plan_train_data_is_what_collate_makes_of_the_item():
+  plan, data = sc.planned(16, 16, 0, 3, 3)
+  for k, v in plan['train_data'].items():
+    assert v.dtype == data[k].dtype and tuple(v.shape) == tuple(data[k].shape) and torch.equal(v, data[k]), k
+
+
+def test_value_errors_without_a_device():
+  a = sc.make_scene(16, 16, 1)
+  make = lambda dev='cpu', **over: scene_mod.DeviceScene(dev, *[{**a, **over}[k] for k in (
+      'images', 'intrinsics', 'poses', 'depth_range', 'disp', 'motion_mask', 'static_mask', 'flows', 'flow_masks', 'virtual_views', 'virtual_poses',
+      'source_masks')])
+  with pytest.raises(ValueError, match='no CPU fallback'):
+    make()
+  with pytest.raises(ValueError, match='at least 7 frames'):
+    scene_mod.DeviceScene('cpu', a['images'][:6], a['intrinsics'][:6], a['poses'][:6], a['depth_range'], a['disp'][:6], a['motion_mask'][:6],
+                          a['static_mask'][:6], a['flows'][:6], a['flow_masks'][:6], a['virtual_views'][:6], a['virtual_poses'][:6])
+  for over, match in ((dict(images=a['images'].astype(np.float32)), 'images must be uint8'), (dict(images=a['images'][..., :2]), 'images must be uint8'),
+                      (dict(disp=a['disp'].astype(np.float64)), 'disp must be float32'), (dict(disp=a['disp'][:, :-1]), 'disp must be'),
+                      (dict(flows=a['flows'][:, :5]), 'flows must be'), (dict(flow_masks=a['flow_masks'] * np.uint8(2)), 'only 0 and 1'),
+                      (dict(motion_mask=a['motion_mask'].astype(np.int64)), 'uint8, bool or float32'), (dict(poses=a['poses'][:, :3]), 'poses must be'),
+                      (dict(virtual_poses=a['virtual_poses'][:, :7]), 'virtual_poses must be'), (dict(virtual_views=a['virtual_views'][:, :7]), 'virtual_views must be'),
+                      (dict(source_masks=a['source_masks'][:, :-1]), 'source_masks must be'), (dict(images='frames'), 'numpy array or a torch tensor')):
+    with pytest.raises(ValueError, match=match):
+      make(**over)
+  s = _host_scene(9)
+  with pytest.raises(ValueError, match='num_vv=9'):
+    s.plan(0, sc.args_of(num_vv=9))
+  with pytest.raises(ValueError, match='without source_masks'):
+    s.plan(0, sc.args_of(mask_src_view=True))
+  with pytest.raises(ValueError, match='at most 32'):
+    s.plan(0, sc.args_of(num_source_views=17, max_range=40))
+  with pytest.raises(ValueError, match='more than 32'):
+    s.descriptors(3, 4, [4, 5, 6, 2, 1, 0], [3, 5], list(range(9)) * 4, [], [], False)
+  with pytest.raises(ValueError, match='empty'):
+    s.descriptors(3, 4, [4, 5, 6, 2, 1, 0], [3, 5], [], [], [], False)
