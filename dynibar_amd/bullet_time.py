@@ -1,0 +1,89 @@
+"""The loop body of the reference's ``render_monocular_bt.py`` (:297-361) on a device-resident scene: the frames of a bullet-time video -- the
+scene at one time ``render_idx`` seen from a path of cameras -- as uint8 images, without the script's per-frame host work.
+
+    scene = DeviceScene.for_rendering(device, images_u8, intrinsics, c2w_mats, (near_depth, far_depth), virtual_views_u8, src_vv_c2w_mats,
+                                      source_masks=dynamic_masks_u8 if args.mask_src_view else None)      # once per scene
+    for frame in bullet_time.frames(scene, model, projector, args, render_c2w_mats, render_intrinsics, args.render_idx):
+      imageio.imwrite(..., frame[0])                         # [K, h, w, 3] uint8, K = len(outputs); copy it to keep it
+
+Per frame: ``scene.bullet_time_plan`` (the script's view selection, host integers), ``scene.frame_sampler(plan).get_all()`` (two launches, one
+asynchronous host-to-device copy of a few hundred bytes), the two encoder calls and ``render_single_image_mono`` with the script's arguments
+(its frame kept on the device: ``frame_outputs='device'``), ``scene.pack_frames`` (clip, scale, truncate, crop: one kernel) and one
+asynchronous device-to-host copy of the packed bytes into a pinned buffer.  Frame i is yielded while frame i + 1 is already queued, once the
+event behind its copy has completed.  Nothing is written to disk here."""
+from __future__ import annotations
+
+import copy
+
+import torch
+
+from . import render_image
+
+SLOTS = 3  # pinned output buffers in rotation: a yielded frame stays valid until SLOTS - 1 further frames have been asked for
+
+
+def frames(scene, model, projector, args, render_poses, render_intrinsics, render_idx, outputs=('rgb',), with_gt=False, crop_ratio=0.03):
+  """Generator over the frames of the camera path ``render_poses`` / ``render_intrinsics`` (``[F, 4, 4]`` each, ``batch_parse_llff_poses`` of the
+  script's render poses).  outputs: 1..4 keys of ``ret['outputs_coarse_ref']`` (``rgb``, ``rgb_static``, ``rgb_dy``); with_gt: stored frame i is the
+  left half of frame i's images, like the script's ``full_rgb`` (the path must then be no longer than the scene).
+  Yields numpy uint8 ``[K, H - 2 crop_h, (W - 2 crop_w) * (2 if with_gt else 1), 3]``: a view of a pinned buffer that is reused later."""
+  outputs = tuple(outputs)
+  if not 1 <= len(outputs) <= 4:
+    raise ValueError(f'outputs names 1..4 images of outputs_coarse_ref, got {len(outputs)}')
+  if len(render_poses) != len(render_intrinsics):
+    raise ValueError(f'{len(render_poses)} render poses but {len(render_intrinsics)} intrinsics')
+  dev = scene.device
+  render_args = copy.copy(args)
+  render_args.frame_outputs = 'device'
+  on_device = dev.type == 'cuda'
+  slots = [None] * SLOTS   # (pinned buffer, event of the copy into it)
+  pending = None           # the slot of the frame that is queued but not yet yielded
+  ref_time_embedding = None
+
+  def finished(slot):
+    buf, ev = slot
+    if ev is not None:
+      ev.synchronize()
+    return buf.numpy()
+
+  for i in range(len(render_poses)):
+    plan = scene.bullet_time_plan(render_poses[i], render_intrinsics[i], render_idx, args, gt_frame=i if with_gt else None)
+    if ref_time_embedding is None:  # (render_idx is the same for every frame of the path: uploaded once)
+      ref_time_embedding = plan['data']['ref_time'].to(dev)
+    ref_frame_idx = plan['render_idx']
+    ref_time_offset = [int(near_idx - ref_frame_idx) for near_idx in plan['nearest_pose_ids'].tolist()]
+    if hasattr(model, 'switch_to_eval'):
+      model.switch_to_eval()
+    with torch.no_grad():
+      ray_sampler = scene.frame_sampler(plan)
+      ray_batch = ray_sampler.get_all()
+      cb_featmaps_1, _ = model.feature_net(ray_batch['src_rgbs'].squeeze(0).permute(0, 3, 1, 2))
+      static_featmaps, _ = model.feature_net_st(ray_batch['static_src_rgbs'].squeeze(0).permute(0, 3, 1, 2))
+      ret = render_image.render_single_image_mono(
+          frame_idx=(ref_frame_idx, None), time_embedding=(ref_time_embedding, None), time_offset=(ref_time_offset, None),
+          ray_sampler=ray_sampler, ray_batch=ray_batch, model=model, projector=projector, chunk_size=args.chunk_size, det=True,
+          N_samples=args.N_samples, args=render_args, inv_uniform=args.inv_uniform, N_importance=args.N_importance, white_bkgd=args.white_bkgd,
+          featmaps=(cb_featmaps_1, None, static_featmaps), is_train=False, num_vv=args.num_vv)
+      group = ret['outputs_coarse_ref']
+      packed = scene.pack_frames([group[k] for k in outputs], crop_ratio=crop_ratio, gt_frame=plan['gt_frame'])
+    j = i % SLOTS
+    if slots[j] is None or tuple(slots[j][0].shape) != tuple(packed.shape):
+      slots[j] = (torch.empty(packed.shape, dtype=torch.uint8, pin_memory=on_device), torch.cuda.Event() if on_device else None)
+    buf, ev = slots[j]
+    with torch.cuda.device(dev) if on_device else _Null():
+      buf.copy_(packed, non_blocking=True)  # the frame's one device-to-host copy
+      if ev is not None:
+        ev.record()
+    if pending is not None:
+      yield finished(pending)
+    pending = slots[j]
+  if pending is not None:
+    yield finished(pending)
+
+
+class _Null(object):
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *a):
+    return False

@@ -12,7 +12,9 @@
 //                        the dword loads are aligned whatever H*W*3 is; the float4 stores are used where view v of the OUTPUT starts on
 //                        16 bytes (always when H*W*3 is a multiple of 4), four scalar stores otherwise.  The last H*W*3 mod 4 values are
 //                        a scalar tail.  A one-channel mask is read per byte (two pixels at most per dword, cached), a three-channel mask
-//                        as the image's own dword.  Workgroup 0 of a view writes its camera [H, W, K(16), c2w(16)].
+//                        as the image's own dword.  Workgroup 0 of a view writes its camera [H, W, K(16), c2w(16)].  With a target
+//                        camera (dyn_scene_views_target: a frame rendered from a camera that is not one of the scene's, dyn_bullet.h) a
+//                        view whose intrinsics frame is -1 takes K from that camera; without one -1 is a bad index like any other.
 //   k_scene_supervision  one thread per selected pixel: ray (dyn_ray_basis / dyn_ray_dir, the code of k_image_rays: the same bits), pixel
 //                        coordinates, rgb / 255, and copies of disparity, the two masks, the six flows and their masks.  Thread-sized
 //                        gathers of a random pixel set (its measured time: DESIGN.md section 4.10).  Workgroup 0 also writes the two cameras.
@@ -28,25 +30,27 @@
 
 __device__ __forceinline__ float scn_unit(unsigned b) { return (float)b / 255.0f; }
 
-__device__ __forceinline__ void scn_camera(const DynSceneStore& s, int pose_frame, int virt, int intr_frame, float* __restrict__ cam, int t) {
+// intr_frame -1 (dyn_scene_views_target only): K of the target camera, a [34] array laid out like cam itself
+__device__ __forceinline__ void scn_camera(const DynSceneStore& s, int pose_frame, int virt, int intr_frame, float* __restrict__ cam, int t,
+                                           const float* __restrict__ target_camera = nullptr) {
   if (t == 0) cam[0] = (float)s.H;
   else if (t == 1) cam[1] = (float)s.W;
-  else if (t < 18) cam[t] = s.intrinsics[(long)intr_frame * 16 + (t - 2)];
+  else if (t < 18) cam[t] = intr_frame < 0 ? target_camera[t] : s.intrinsics[(long)intr_frame * 16 + (t - 2)];
   else if (t < 34) cam[t] = virt >= 0 ? s.vposes[((long)pose_frame * 8 + virt) * 16 + (t - 18)] : s.poses[(long)pose_frame * 16 + (t - 18)];
 }
 
 __global__ __launch_bounds__(SCN_THREADS) void k_scene_views(DynSceneStore s, const int32_t* __restrict__ desc, float* __restrict__ images,
-                                                             float* __restrict__ cameras) {
+                                                             float* __restrict__ cameras, const float* __restrict__ target_camera) {
   const int v = blockIdx.y, tid = threadIdx.x;
   const int frame = desc[v * 4], virt = desc[v * 4 + 1], mframe = desc[v * 4 + 2], kframe = desc[v * 4 + 3];
   const bool ok = frame >= 0 && frame < s.N && virt >= -1 && virt < 8 && (virt < 0 || (s.vviews && s.vposes)) && mframe >= -1 && mframe < s.N &&
-                  (mframe < 0 || s.src_masks) && kframe >= 0 && kframe < s.N;
+                  (mframe < 0 || s.src_masks) && kframe >= (target_camera ? -1 : 0) && kframe < s.N;
   const long n = (long)s.H * s.W * 3;  // values of one image
   const long ndw = n >> 2;
   float* __restrict__ out = images + (long)v * n;
   const bool vec = ((((long)v * n) & 3) == 0) && ((reinterpret_cast<uintptr_t>(images) & 15) == 0);
   if (blockIdx.x == 0 && tid < 34) {
-    if (ok) scn_camera(s, frame, virt, kframe, cameras + v * 34, tid);
+    if (ok) scn_camera(s, frame, virt, kframe, cameras + v * 34, tid, target_camera);
     else cameras[v * 34 + tid] = 0.f;
   }
   const uint8_t* img = nullptr;
@@ -170,28 +174,54 @@ static int scn_check_store(const DynSceneStore* s, const char* who) {
   return 0;
 }
 
-extern "C" int dyn_scene_views(const DynSceneStore* s, const int32_t* desc_host, const int32_t* desc, int V_ref, int V_anchor, int V_static,
-                               float* images, float* cameras, void* stream) {
-  if (int rc = scn_check_store(s, "dyn_scene_views")) return rc;
-  DYN_REQUIRE(desc_host && desc && images && cameras, "dyn_scene_views: desc_host, desc, images and cameras are required");
-  DYN_REQUIRE(V_ref >= 0 && V_anchor >= 0 && V_static >= 0 && V_ref + V_anchor + V_static >= 1, "dyn_scene_views: view counts %d, %d, %d", V_ref,
+// The argument check and the launch of both entry points.  tcam_host / tcam: the target camera (host copy, DEVICE array) or null, and
+// with null an intrinsics frame of -1 is refused like any other index out of range.
+static int scn_views_launch(const char* who, const DynSceneStore* s, const int32_t* desc_host, const int32_t* desc, int V_ref, int V_anchor,
+                            int V_static, const float* tcam_host, const float* tcam, float* images, float* cameras, void* stream) {
+  if (int rc = scn_check_store(s, who)) return rc;
+  DYN_REQUIRE(desc_host && desc && images && cameras, "%s: desc_host, desc, images and cameras are required", who);
+  DYN_REQUIRE(V_ref >= 0 && V_anchor >= 0 && V_static >= 0 && V_ref + V_anchor + V_static >= 1, "%s: view counts %d, %d, %d", who, V_ref,
               V_anchor, V_static);
   DYN_REQUIRE(V_ref <= SCN_MAX_VIEWS && V_anchor <= SCN_MAX_VIEWS && V_static <= SCN_MAX_VIEWS,
-              "dyn_scene_views: %d, %d, %d views in the lists (at most %d per list)", V_ref, V_anchor, V_static, SCN_MAX_VIEWS);
+              "%s: %d, %d, %d views in the lists (at most %d per list)", who, V_ref, V_anchor, V_static, SCN_MAX_VIEWS);
   const int V = V_ref + V_anchor + V_static;
+  const int kmin = tcam ? -1 : 0;
   for (int v = 0; v < V; ++v) {
     const int32_t* d = desc_host + v * 4;
-    DYN_REQUIRE(d[0] >= 0 && d[0] < s->N, "dyn_scene_views: view %d: image frame %d is outside 0..%d", v, d[0], s->N - 1);
-    DYN_REQUIRE(d[1] >= -1 && d[1] < 8, "dyn_scene_views: view %d: virtual index %d is outside -1..7", v, d[1]);
-    DYN_REQUIRE(d[1] < 0 || (s->vviews && s->vposes), "dyn_scene_views: view %d is a virtual view but the store has none", v);
-    DYN_REQUIRE(d[2] >= -1 && d[2] < s->N, "dyn_scene_views: view %d: mask frame %d is outside -1..%d", v, d[2], s->N - 1);
-    DYN_REQUIRE(d[2] < 0 || s->src_masks, "dyn_scene_views: view %d asks for a source mask but the store has none", v);
-    DYN_REQUIRE(d[3] >= 0 && d[3] < s->N, "dyn_scene_views: view %d: intrinsics frame %d is outside 0..%d", v, d[3], s->N - 1);
+    DYN_REQUIRE(d[0] >= 0 && d[0] < s->N, "%s: view %d: image frame %d is outside 0..%d", who, v, d[0], s->N - 1);
+    DYN_REQUIRE(d[1] >= -1 && d[1] < 8, "%s: view %d: virtual index %d is outside -1..7", who, v, d[1]);
+    DYN_REQUIRE(d[1] < 0 || (s->vviews && s->vposes), "%s: view %d is a virtual view but the store has none", who, v);
+    DYN_REQUIRE(d[2] >= -1 && d[2] < s->N, "%s: view %d: mask frame %d is outside -1..%d", who, v, d[2], s->N - 1);
+    DYN_REQUIRE(d[2] < 0 || s->src_masks, "%s: view %d asks for a source mask but the store has none", who, v);
+    DYN_REQUIRE(d[3] >= kmin && d[3] < s->N, "%s: view %d: intrinsics frame %d is outside %d..%d", who, v, d[3], kmin, s->N - 1);
   }
   const long ndw = ((long)s->H * s->W * 3) >> 2;
-  DYN_LAUNCH(DYN_K_SCENE_VIEWS, "dyn_scene_views", k_scene_views, dim3(dyn_cdiv(ndw + 1, SCN_THREADS * SCN_UNROLL), V), dim3(SCN_THREADS), 0,
-             (hipStream_t)stream, *s, desc, images, cameras);
+  DYN_LAUNCH(DYN_K_SCENE_VIEWS, who, k_scene_views, dim3(dyn_cdiv(ndw + 1, SCN_THREADS * SCN_UNROLL), V), dim3(SCN_THREADS), 0,
+             (hipStream_t)stream, *s, desc, images, cameras, tcam);
   return 0;
+}
+
+extern "C" int dyn_scene_views(const DynSceneStore* s, const int32_t* desc_host, const int32_t* desc, int V_ref, int V_anchor, int V_static,
+                               float* images, float* cameras, void* stream) {
+  return scn_views_launch("dyn_scene_views", s, desc_host, desc, V_ref, V_anchor, V_static, nullptr, nullptr, images, cameras, stream);
+}
+
+extern "C" int dyn_scene_views_target(const DynSceneStore* s, const int32_t* desc_host, const int32_t* desc, int V_ref, int V_anchor, int V_static,
+                                      const float* target_camera_host, const float* target_camera, float* images, float* cameras, void* stream) {
+  const char* who = "dyn_scene_views_target";
+  if (int rc = scn_check_store(s, who)) return rc;
+  DYN_REQUIRE((target_camera_host != nullptr) == (target_camera != nullptr), "%s: target_camera and its host copy go together", who);
+  if (target_camera_host) {
+    DYN_REQUIRE(target_camera_host[0] == (float)s->H && target_camera_host[1] == (float)s->W,
+                "%s: the target camera is %g x %g, the scene's images are not", who, (double)target_camera_host[0], (double)target_camera_host[1]);
+    for (int i = 2; i < 34; ++i) DYN_REQUIRE(target_camera_host[i] - target_camera_host[i] == 0.f, "%s: target camera entry %d is not finite", who, i);
+  } else if (desc_host) {  // the one refusal that is this entry point's own: name the missing camera, not a range
+    const int V = V_ref + V_anchor + V_static;
+    if (V_ref >= 0 && V_anchor >= 0 && V_static >= 0 && V_ref <= SCN_MAX_VIEWS && V_anchor <= SCN_MAX_VIEWS && V_static <= SCN_MAX_VIEWS)
+      for (int v = 0; v < V; ++v)
+        DYN_REQUIRE(desc_host[v * 4 + 3] != -1, "%s: view %d takes the target camera's intrinsics (-1) but no target camera was given", who, v);
+  }
+  return scn_views_launch(who, s, desc_host, desc, V_ref, V_anchor, V_static, target_camera_host, target_camera, images, cameras, stream);
 }
 
 extern "C" int dyn_scene_supervision(const DynSceneStore* s, const DynSceneSupervisionParams* p, void* stream) {

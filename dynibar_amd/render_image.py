@@ -15,7 +15,9 @@ Output contract.  The reference copies EVERY tensor of EVERY chunk to the host (
     caches it).  A caller that reads an entry gets exactly what the reference returns; a caller that does not pays nothing.
     With world_size > 1 the access issues a collective, so ranks must read the same entries in the same order (SPMD callers do).
 ``FRAME_OUTPUTS = 'all'`` (or ``args.frame_outputs`` / env ``DYNIBAR_FRAME_OUTPUTS``) restores the eager behaviour: everything is
-assembled before the call returns, with one packed collective per group.
+assembled before the call returns, with one packed collective per group.  ``'device'`` is ``'lazy'`` without the copy to the host: the
+entries are the same values as device tensors, for a consumer that stays on the device (``dynibar_amd.bullet_time`` packs them to uint8
+there); nothing is copied and the call does not wait for the frame.
 """
 from __future__ import annotations
 
@@ -279,8 +281,8 @@ class FrameOutputs(OrderedDict):
 
 def _frame_mode(args):
   mode = getattr(args, 'frame_outputs', None) or os.environ.get('DYNIBAR_FRAME_OUTPUTS') or FRAME_OUTPUTS
-  if mode not in ('lazy', 'all'):
-    raise ValueError(f"frame_outputs must be 'lazy' or 'all', got {mode!r}")
+  if mode not in ('lazy', 'all', 'device'):
+    raise ValueError(f"frame_outputs must be 'lazy', 'all' or 'device', got {mode!r}")
   return mode
 
 
@@ -291,8 +293,9 @@ def _shape_frame(t, Hs, Ws):
   return t.reshape((Hs, Ws, -1)).squeeze()
 
 
-def _assemble(per_chunk, n_rays, Hs, Ws, dist, world, rank, count=None, eager=None):
-  """list of per-chunk output dicts of this rank's tile -> FrameOutputs of the full frame.  eager: keys assembled now (None: all)."""
+def _assemble(per_chunk, n_rays, Hs, Ws, dist, world, rank, count=None, eager=None, resident=False):
+  """list of per-chunk output dicts of this rank's tile -> FrameOutputs of the full frame.  eager: keys assembled now (None: all).
+  resident: the entries stay device tensors (nothing is copied, nothing synchronises): the same values, for a consumer on the device."""
   frame = FrameOutputs()
   keys = list(per_chunk[0].keys()) if per_chunk else []
   local = OrderedDict()
@@ -312,7 +315,7 @@ def _assemble(per_chunk, n_rays, Hs, Ws, dist, world, rank, count=None, eager=No
   def fetch(ks):
     t0 = _clock() if FRAME_STATS is not None else 0.0
     full = gather_rows(OrderedDict((k, local[k]) for k in ks), n_rays, dist, world, rank, count)
-    host = OrderedDict((k, _shape_frame(t, Hs, Ws)) for k, t in _to_host(full).items())
+    host = OrderedDict((k, _shape_frame(t, Hs, Ws)) for k, t in (full if resident else _to_host(full)).items())
     if FRAME_STATS is not None and ks:
       tile = ray_tile(n_rays, world, rank)[2]
       FRAME_STATS['gather_ms'] = FRAME_STATS.get('gather_ms', 0.0) + (_clock() - t0) * 1e3
@@ -320,13 +323,15 @@ def _assemble(per_chunk, n_rays, Hs, Ws, dist, world, rank, count=None, eager=No
     return host
 
   def blank(rgb, mask):
+    if resident:  # (the same pixels without the synchronisation of boolean indexing; a copy: the entry may alias a chunk's own output)
+      return rgb.masked_fill((mask == 0).unsqueeze(-1), 0.0)
     rgb[mask == 0] = 0.0  # render_image.py:162-164, :186-188: pixels whose ray mask is off are zeroed, in every group
     return rgb
 
   for k, t in fetch(now).items():
     frame[k] = t
   if 'rgb' in now and 'mask' in now:
-    blank(OrderedDict.__getitem__(frame, 'rgb'), OrderedDict.__getitem__(frame, 'mask'))
+    frame['rgb'] = blank(OrderedDict.__getitem__(frame, 'rgb'), OrderedDict.__getitem__(frame, 'mask'))
 
   def late(k):
     if k == 'rgb' and 'mask' in local:  # the blanking needs the ray mask: both travel together
@@ -471,7 +476,7 @@ def _frame(chunks, groups, primary, n_rays, Hs, Ws, dist, world, rank, count, mo
       all_ret[g] = OrderedDict()
       continue
     eager = None if mode == 'all' else (_EAGER_KEYS if g == primary else ())
-    all_ret[g] = _assemble(chunks[g], n_rays, Hs, Ws, dist, world, rank, count, eager)
+    all_ret[g] = _assemble(chunks[g], n_rays, Hs, Ws, dist, world, rank, count, eager, resident=(mode == 'device'))
   all_ret['outputs_fine'] = None
   return all_ret
 

@@ -21,6 +21,15 @@ What stays host work of the caller, once per scene: reading and decoding the fil
 (monocular.py:177-204) and ``disp / scale``.  cv2, skimage and imageio were not available when this was written, so their semantics are not
 restated here: the arrays are taken as the caller's own loader produces them.
 
+Bullet-time frames (render_monocular_bt.py) come from the same resident scene, which then needs no training stores:
+
+    scene = DeviceScene.for_rendering(device, images, intrinsics, poses, depth_range, virtual_views, virtual_poses, source_masks)
+    plan = scene.bullet_time_plan(render_pose, render_intrinsics, render_idx, args, gt_frame=i)   # DynamicVideoDataset.__getitem__'s selection
+    ray_batch = scene.frame_sampler(plan).get_all()      # RaySamplerSingleImage(data, device).get_all(): keys, shapes, dtypes, bits
+    packed = scene.pack_frames([rgb, rgb_static, rgb_dy], crop_ratio, gt_frame=i)                 # the script's output stage, uint8 on the device
+
+(``dynibar_amd.bullet_time.frames`` is the loop around them.)
+
 Host traffic per batch: the plan's descriptors and the pixel indices go through one pinned staging buffer -- one asynchronous host-to-device
 copy, no device-to-host copy and no synchronisation.  There is no CPU fallback: without the library or a HIP device this module raises.
 """
@@ -77,6 +86,15 @@ def _binary_u8(x, want, what):
   return np.ascontiguousarray(x.astype(np.uint8))
 
 
+_TRAINING_STORES = ('disp', 'motion_mask', 'static_mask', 'flows', 'flow_masks')
+
+
+def _need_training_stores(scene, what):
+  missing = getattr(scene, 'missing_stores', ())
+  if missing:
+    raise ValueError(f'{what} needs the training stores {", ".join(missing)}: this scene was made by DeviceScene.for_rendering without them')
+
+
 def nearest_pose_ids_dist(tar_pose, ref_poses, tar_id):
   """``get_nearest_pose_ids(tar_pose, ref_poses, tar_id=tar_id, angular_dist_method='dist')`` (ibrnet/data_loaders/data_utils.py:85-120)"""
   num_cams = len(ref_poses)
@@ -88,6 +106,14 @@ def nearest_pose_ids_dist(tar_pose, ref_poses, tar_id):
     assert tar_id < num_cams
     dists[tar_id] = 1e3
   return np.argsort(dists)
+
+
+def interval_pose_ids_dist(tar_pose, ref_poses, interval):
+  """``get_interval_pose_ids(tar_pose, ref_poses, tar_id=-1, angular_dist_method='dist', interval=interval)`` (data_utils.py:123-165): the
+  distance ordering of every ``interval``-th pose, as indices into the full list"""
+  original_indices = np.array(range(0, len(ref_poses)))
+  subsample_indices = original_indices[::interval]
+  return subsample_indices[nearest_pose_ids_dist(tar_pose, ref_poses[::interval], -1)]
 
 
 class DeviceScene(object):
@@ -108,6 +134,19 @@ class DeviceScene(object):
 
   def __init__(self, device, images, intrinsics, poses, depth_range, disp, motion_mask, static_mask, flows, flow_masks, virtual_views,
                virtual_poses, source_masks=None):
+    self._setup(device, images, intrinsics, poses, depth_range, (disp, motion_mask, static_mask, flows, flow_masks), virtual_views, virtual_poses,
+                source_masks)
+
+  @classmethod
+  def for_rendering(cls, device, images, intrinsics, poses, depth_range, virtual_views, virtual_poses, source_masks=None):
+    """A scene for ``bullet_time_plan`` / ``frame_sampler`` / ``pack_frames`` only: the arguments of the constructor without the training-only
+    stores (disparity, motion and static masks, flows, flow masks).  ``plan``, ``sampler`` and ``assemble`` raise ValueError on it."""
+    self = cls.__new__(cls)
+    self._setup(device, images, intrinsics, poses, depth_range, None, virtual_views, virtual_poses, source_masks)
+    return self
+
+  def _setup(self, device, images, intrinsics, poses, depth_range, training, virtual_views, virtual_poses, source_masks):
+    """the constructor's checks and uploads; training: (disp, motion_mask, static_mask, flows, flow_masks), or None (for_rendering)"""
     self.device = torch.device(device)
     images = _np(images, 'images')
     if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
@@ -120,18 +159,22 @@ class DeviceScene(object):
     self.N, self.H, self.W = N, H, W
     self.intrinsics_host = _shape(_np(intrinsics, 'intrinsics'), (N, 4, 4), 'intrinsics')
     self.poses_host = _shape(_np(poses, 'poses'), (N, 4, 4), 'poses')
-    disp = _shape(_np(disp, 'disp'), (N, H, W), 'disp')
-    flows = _shape(_np(flows, 'flows'), (N, 6, H, W, 2), 'flows')
-    for x, what in ((disp, 'disp'), (flows, 'flows')):
-      if x.dtype != np.float32:
-        raise ValueError(f'{what} must be float32, got {x.dtype}')
-    motion_mask = _binary_u8(motion_mask, (N, H, W), 'motion_mask')
-    static_mask = _binary_u8(static_mask, (N, H, W), 'static_mask')
-    flow_masks = _binary_u8(flow_masks, (N, 6, H, W), 'flow_masks')
+    self.missing_stores = () if training is not None else _TRAINING_STORES
+    if training is not None:
+      disp, motion_mask, static_mask, flows, flow_masks = training
+      disp = _shape(_np(disp, 'disp'), (N, H, W), 'disp')
+      flows = _shape(_np(flows, 'flows'), (N, 6, H, W, 2), 'flows')
+      for x, what in ((disp, 'disp'), (flows, 'flows')):
+        if x.dtype != np.float32:
+          raise ValueError(f'{what} must be float32, got {x.dtype}')
+      motion_mask = _binary_u8(motion_mask, (N, H, W), 'motion_mask')
+      static_mask = _binary_u8(static_mask, (N, H, W), 'static_mask')
+      flow_masks = _binary_u8(flow_masks, (N, 6, H, W), 'flow_masks')
     virtual_views = _shape(_np(virtual_views, 'virtual_views'), (N, NUM_VIRTUAL, H, W, 3), 'virtual_views')
     if virtual_views.dtype != np.uint8:
       raise ValueError(f'virtual_views must be uint8, got {virtual_views.dtype}')
     virtual_poses = _shape(_np(virtual_poses, 'virtual_poses'), (N, NUM_VIRTUAL, 4, 4), 'virtual_poses')
+    self.virtual_poses_host = virtual_poses  # as given: bullet_time_plan computes its distances in the caller's dtype
     mask_channels = 1
     if source_masks is not None:
       source_masks = _np(source_masks, 'source_masks')
@@ -144,6 +187,8 @@ class DeviceScene(object):
       raise ValueError(f'DeviceScene needs a HIP device (cuda:N), got {self.device}: there is no CPU fallback')
     near, far = depth_range
     self.depth_range = torch.tensor([[near * 0.9, far * 1.5]]).float().to(self.device)  # [1, 2]: the collated form
+    # (the bullet-time item has no .float(), render_monocular_bt.py:245: the script's numpy doubles stay float64 through default_collate)
+    self.depth_range_f64 = torch.tensor([[float(near) * 0.9, float(far) * 1.5]], dtype=torch.float64).to(self.device)
 
     dev = self.device
     self._frames, image_stride = self._padded(images.reshape(N, -1))
@@ -154,9 +199,13 @@ class DeviceScene(object):
     self._intrinsics = f32(self.intrinsics_host.reshape(N, 16))
     self._poses = f32(self.poses_host.reshape(N, 16))
     self._vposes = f32(virtual_poses.reshape(N, NUM_VIRTUAL, 16))
-    self._disp, self._flows = f32(disp), f32(flows)
-    self._motion_mask, self._static_mask, self._flow_masks = u8(motion_mask), u8(static_mask), u8(flow_masks)
+    self._disp = self._flows = self._motion_mask = self._static_mask = self._flow_masks = None
+    if training is not None:
+      self._disp, self._flows = f32(disp), f32(flows)
+      self._motion_mask, self._static_mask, self._flow_masks = u8(motion_mask), u8(static_mask), u8(flow_masks)
     self.has_source_masks = source_masks is not None
+    self._image_stride = image_stride
+    self._uv_grid = None
     self._store = params('DynSceneStore', N=N, H=H, W=W, image_stride=image_stride, frames=_p(self._frames), vviews=_p(self._vviews),
                          src_masks=_p(self._src_masks), mask_channels=mask_channels, mask_stride=mask_stride, intrinsics=_p(self._intrinsics),
                          poses=_p(self._poses), vposes=_p(self._vposes), disp=_p(self._disp), motion_mask=_p(self._motion_mask),
@@ -179,6 +228,7 @@ class DeviceScene(object):
     -> dict: ``idx``, ``anchor_idx``, ``nearest_pose_ids``, ``anchor_nearest_pose_ids``, ``static_pose_ids``, ``ref_virtual``, ``anchor_virtual``,
     ``counts`` (views in the ref, anchor and static lists), ``desc`` (int32 ``[V, 4]`` for dyn_scene_views: image frame, virtual index or -1, mask
     frame or -1, intrinsics frame) and ``train_data``, the non-image entries of the collated item that train.py reads."""
+    _need_training_stores(self, 'plan')
     num_frames = self.N
     num_frames_sample = int(args.num_source_views)
     num_vv = int(args.num_vv)
@@ -255,6 +305,7 @@ class DeviceScene(object):
     return np.asarray(ref_list + anchor_list + static_list, dtype=np.int32).reshape(-1, 4), counts
 
   def sampler(self, plan):
+    _need_training_stores(self, 'sampler')
     return DeviceRaySampler(self, plan)
 
   # ---- one batch ------------------------------------------------------------------------------------------------------------------
@@ -279,6 +330,7 @@ class DeviceScene(object):
   def assemble(self, desc, counts, frame, anchor_frame, sel):
     """The two launches of one batch.  desc int32 ``[V, 4]``, counts the sizes of the three lists, sel the pixel indices (None: all ``H*W``).
     -> (images ``[V, H, W, 3]``, cameras ``[V, 34]``, dict of the per-pixel tensors and the two cameras).  Nothing synchronises."""
+    _need_training_stores(self, 'assemble')
     H, W, dev = self.H, self.W, self.device
     desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 4)
     V = int(desc.shape[0])
@@ -324,6 +376,189 @@ class DeviceScene(object):
                **{k: _p(v) for k, v in px.items()})
     call('dyn_scene_supervision', ctypes.byref(self._store), ctypes.byref(p), st)
     return images, cameras, px
+
+
+  # ---- bullet-time frames (render_monocular_bt.py) --------------------------------------------------------------------------------
+  def bullet_time_plan(self, render_pose, render_intrinsics, render_idx, args, gt_frame=None):
+    """The view selection of ``DynamicVideoDataset.__getitem__`` (render_monocular_bt.py:97-155, :174-183) for one frame of the video, restated
+    literally: the scene seen at time ``render_idx`` from ``render_pose`` / ``render_intrinsics`` (``[4, 4]`` each), a camera that is not one of
+    the scene's.  args: ``num_source_views``, ``max_range``, ``num_vv``, ``mask_src_view``.  ``gt_frame``: the stored frame the script shows
+    beside the prediction (frame ``idx`` of its loop, :105-106), or None.  Host work only; reads ``N``, ``H``, ``W``, ``poses_host``,
+    ``virtual_poses_host`` and ``has_source_masks``.
+    -> dict: ``render_idx``, ``gt_frame``, ``nearest_pose_ids``, ``virtual_ids``, ``static_pose_ids``, ``counts`` = (7 + num_vv, 0, 2 n + 1),
+    ``desc`` (int32 ``[V, 4]`` for dyn_scene_views_target; a virtual view's intrinsics frame is -1: the render camera's, :195-199), ``camera``
+    (float32 ``[34]``) and ``data``, the non-image entries of the collated item.  Where the reference asserts or goes wrong silently this raises
+    ValueError."""
+    num_frames = int(self.N)
+    n = int(args.num_source_views)
+    max_range = int(args.max_range)
+    num_vv = int(args.num_vv)
+    mask_src_view = bool(getattr(args, 'mask_src_view', False))
+    render_pose, render_intrinsics = _np(render_pose, 'render_pose'), _np(render_intrinsics, 'render_intrinsics')
+    _shape(render_pose, (4, 4), 'render_pose')
+    _shape(render_intrinsics, (4, 4), 'render_intrinsics')
+    render_idx = int(render_idx)
+    if render_idx < 3 or render_idx > num_frames - 4:  # (the reference would wrap around with negative indices or run off the end)
+      raise ValueError(f'render_idx={render_idx} is outside 3..{num_frames - 4}: the temporal views are the frames render_idx - 3 .. render_idx + 3')
+    if num_vv < 0 or num_vv > NUM_VIRTUAL:
+      raise ValueError(f'num_vv={num_vv}: a frame has {NUM_VIRTUAL} virtual views')
+    if mask_src_view and not self.has_source_masks:
+      raise ValueError('args.mask_src_view is set but the scene was made without source_masks')
+    if n < 1 or 2 * n + 1 > MAX_VIEWS:
+      raise ValueError(f'num_source_views={n}: the static list holds 2 n + 1 = {2 * n + 1} views, at least 3 and at most {MAX_VIEWS}')
+    if gt_frame is not None:
+      gt_frame = int(gt_frame)
+      if gt_frame < 0 or gt_frame >= num_frames:
+        raise ValueError(f'gt_frame={gt_frame} is outside the scene (0..{num_frames - 1})')
+    frame_interval = max_range // n
+    if frame_interval < 1:
+      raise ValueError(f'max_range={max_range} // num_source_views={n} gives a frame interval of {frame_interval}: at least 1')
+    train_poses = self.poses_host
+
+    nearest_pose_ids = np.sort([render_idx + offset for offset in [1, 2, 3, 0, -1, -2, -3]])
+    sp_pose_ids = nearest_pose_ids_dist(render_pose, train_poses, -1)
+    static_pose_ids = []
+    interval_pose_ids = interval_pose_ids_dist(render_pose, train_poses, frame_interval)
+    for sp_pose_id in interval_pose_ids:
+      if len(static_pose_ids) >= (n * 2 + 1):
+        break
+      if np.abs(sp_pose_id - render_idx) > (max_range + n * 0.5):
+        continue
+      static_pose_ids.append(sp_pose_id)
+    static_pose_set = set(static_pose_ids)
+    # if there is no sufficient src imgs, naively choose the closest images (the set is the one built BEFORE this fill)
+    for sp_pose_id in sp_pose_ids[::5]:
+      if len(static_pose_ids) >= (n * 2 + 1):
+        break
+      if sp_pose_id in static_pose_set:
+        continue
+      static_pose_ids.append(sp_pose_id)
+    static_pose_ids = np.sort(static_pose_ids)
+    if len(static_pose_ids) != (n * 2 + 1):  # the reference's assert
+      raise ValueError(f'only {len(static_pose_ids)} static views found for render_idx={render_idx}, {2 * n + 1} are needed '
+                       f'(num_source_views={n}, max_range={max_range}, {num_frames} frames)')
+    vv_pose_ids = nearest_pose_ids_dist(render_pose, self.virtual_poses_host[render_idx], -1)
+    virtual_ids = vv_pose_ids[:num_vv]
+
+    desc, counts = bullet_time_descriptors(render_idx, nearest_pose_ids, virtual_ids, static_pose_ids, mask_src_view)
+    camera = np.concatenate(([int(self.H), int(self.W)], render_intrinsics.flatten(), render_pose.flatten())).astype(np.float32)
+    data = {  # what default_collate makes of the item's scalars and id list (batch size 1)
+        'id': torch.tensor([render_idx]), 'ref_time': torch.tensor([float(render_idx / float(num_frames))], dtype=torch.float64),
+        'nearest_pose_ids': torch.from_numpy(np.asarray(nearest_pose_ids, dtype=np.int64))[None],
+    }
+    return dict(render_idx=render_idx, gt_frame=gt_frame, nearest_pose_ids=nearest_pose_ids, virtual_ids=virtual_ids,
+                static_pose_ids=static_pose_ids, counts=counts, desc=desc, camera=camera, data=data)
+
+  def frame_sampler(self, plan):
+    return FrameRaySampler(self, plan)
+
+  def uv_grid(self):
+    """the pixel grid (x, y) of sample_ray.RaySamplerSingleImage, made once per scene by the same operations"""
+    if self._uv_grid is None:
+      ys, xs = torch.meshgrid(torch.arange(self.H, dtype=torch.float32, device=self.device),
+                              torch.arange(self.W, dtype=torch.float32, device=self.device), indexing='ij')
+      self._uv_grid = torch.stack([xs, ys], dim=-1).reshape(-1, 2)
+    return self._uv_grid
+
+  def assemble_frame(self, desc, counts, camera):
+    """The two launches of one bullet-time frame.  desc int32 ``[V, 4]`` in three lists of ``counts`` views (the middle one: the ground-truth
+    frame, or empty), camera float32 ``[34]``.  Descriptors and camera go to the device as bit patterns in ONE asynchronous copy from the
+    pinned staging rotation; nothing comes back, nothing synchronises.
+    -> (images ``[V, H, W, 3]``, cameras ``[V, 34]``, camera ``[1, 34]`` on the device, ray_o, ray_d ``[H*W, 3]``)"""
+    H, W, dev = self.H, self.W, self.device
+    desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 4)
+    V = int(desc.shape[0])
+    counts = tuple(int(c) for c in counts)
+    if len(counts) != 3 or sum(counts) != V or V < 1 or min(counts) < 0:
+      raise ValueError(f'view lists of {counts} for {V} descriptors')
+    if max(counts) > MAX_VIEWS:
+      raise ValueError(f'{max(counts)} views in a list: more than {MAX_VIEWS}')
+    camera = np.ascontiguousarray(camera, dtype=np.float32).reshape(-1)
+    if camera.shape[0] != 34:
+      raise ValueError(f'camera must hold 34 values [H, W, K, c2w], got {camera.shape[0]}')
+    n = 4 * V + 34
+    host, ev, used = self._stage(n)
+    stage = host.numpy()
+    stage[:4 * V] = desc.reshape(-1)
+    stage[4 * V:n] = camera.view(np.int32)
+    ints = torch.empty((n,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev) if dev.type == 'cuda' else _Null():
+      ints.copy_(host[:n], non_blocking=True)  # the frame's one host-to-device copy
+      if ev is not None:
+        ev.record()
+        used[0] = True
+
+    def out(*shape):
+      t = torch.empty(shape, dtype=torch.float32, device=dev)
+      if POISON_SCRATCH:
+        t.fill_(float('nan'))
+      return t
+
+    images, cameras, ray_o, ray_d = out(V, H, W, 3), out(V, 34), out(H * W, 3), out(H * W, 3)
+    cam_dev = ints[4 * V:].view(torch.float32)
+    st = stream_of(ints)
+    hp, dp = host.data_ptr(), ints.data_ptr()
+    call('dyn_scene_views_target', ctypes.byref(self._store), ctypes.c_void_p(hp), ctypes.c_void_p(dp), counts[0], counts[1], counts[2],
+         ctypes.c_void_p(hp + 16 * V), ctypes.c_void_p(dp + 16 * V), _p(images), _p(cameras), st)
+    call('dyn_image_rays', ctypes.c_void_p(dp + 16 * V), H, W, 1, _p(ray_o), _p(ray_d), st)  # the host sampler's own kernel: its bits
+    return images, cameras, cam_dev[None], ray_o, ray_d
+
+  def pack_frames(self, images, crop_ratio=0.03, gt_frame=None, out=None):
+    """The output stage of render_monocular_bt.py:342-361 in one kernel.  images: 1..4 device fp32 tensors ``[H, W, 3]`` (``rgb``,
+    ``rgb_static``, ``rgb_dy`` of ``outputs_coarse_ref``).  -> uint8 ``[K, H - 2 crop_h, (W - 2 crop_w) * (2 if gt_frame is not None else 1), 3]``
+    on the device, ``crop = int(size * crop_ratio)``; every byte is ``(255 * np.clip(x, 0, 1)).astype(np.uint8)`` (NaN: 0), and with ``gt_frame``
+    the cropped stored frame is the left half of every image.  ``out``: a tensor of that shape to write into."""
+    images = list(images)
+    K = len(images)
+    if K < 1 or K > 4:
+      raise ValueError(f'pack_frames takes 1..4 images, got {K}')
+    for i, t in enumerate(images):
+      if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f'image {i} must be a float32 tensor, got {getattr(t, "dtype", type(t).__name__)}')
+      if t.dim() != 3 or t.shape[2] != 3 or tuple(t.shape) != tuple(images[0].shape):
+        raise ValueError(f'image {i} must be [H, W, 3] like the first, got {list(t.shape)}')
+      if t.device != images[0].device or (_lib._REQUIRE_DEVICE and not t.is_cuda):
+        raise ValueError(f'image {i} is on {t.device}: the images must be on one HIP device')
+    images = [t.detach().contiguous() for t in images]
+    H, W = int(images[0].shape[0]), int(images[0].shape[1])
+    if H * W * 3 >= 2 ** 31:
+      raise ValueError(f'image size {H} x {W} is unsupported (H*W*3 < 2^31)')
+    crop_h, crop_w = int(H * crop_ratio), int(W * crop_ratio)
+    hc, wc = H - 2 * crop_h, W - 2 * crop_w
+    if crop_h < 0 or crop_w < 0 or hc < 1 or wc < 1:
+      raise ValueError(f'crop_ratio={crop_ratio} leaves no pixel of {H} x {W}')
+    if gt_frame is not None:
+      gt_frame = int(gt_frame)
+      if (H, W) != (self.H, self.W):
+        raise ValueError(f'the images are {H} x {W}, the stored frames {self.H} x {self.W}')
+      if gt_frame < 0 or gt_frame >= self.N:
+        raise ValueError(f'gt_frame={gt_frame} is outside the scene (0..{self.N - 1})')
+    shape = (K, hc, wc * (2 if gt_frame is not None else 1), 3)
+    if out is None:
+      out = torch.empty(shape, dtype=torch.uint8, device=images[0].device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous()
+          or out.device != images[0].device):
+      raise ValueError(f'out must be a contiguous uint8 tensor {list(shape)} on {images[0].device}')
+    p = params('DynFramePackParams', K=K, H=H, W=W, crop_h=crop_h, crop_w=crop_w, gt_frame=-1 if gt_frame is None else gt_frame, N=self.N,
+               frames=_p(self._frames) if gt_frame is not None else None, image_stride=self._image_stride, out=_p(out),
+               **{f'image{i}': _p(t) for i, t in enumerate(images)})
+    call('dyn_frame_pack_u8', ctypes.byref(p), stream_of(out))
+    return out
+
+
+def bullet_time_descriptors(render_idx, nearest_pose_ids, virtual_ids, static_pose_ids, mask_src_view):
+  """The two source-view lists of render_monocular_bt.py:157-243 as dyn_scene_views_target descriptors -> (int32 ``[V, 4]``, (ref, 0, static)
+  sizes): there is no anchor list.  A virtual view is image and pose ``virtual_poses[render_idx][v]`` with the RENDER camera's intrinsics
+  (:195-199): intrinsics frame -1.  The temporal and the static views take their own frame's."""
+  render_idx = int(render_idx)
+  ref_list = [(int(i), -1, -1, int(i)) for i in nearest_pose_ids] + [(render_idx, int(v), -1, -1) for v in virtual_ids]
+  static_list = [(int(i), -1, int(i) if mask_src_view else -1, int(i)) for i in static_pose_ids]
+  counts = (len(ref_list), 0, len(static_list))
+  if counts[0] == 0 or counts[2] == 0:
+    raise ValueError(f'an empty source-view list: {counts[0]} temporal and virtual views, {counts[2]} static views')
+  if max(counts) > MAX_VIEWS:
+    raise ValueError(f'{max(counts)} views in a list: more than {MAX_VIEWS}')
+  return np.asarray(ref_list + static_list, dtype=np.int32).reshape(-1, 4), counts
 
 
 class _Null(object):
@@ -410,3 +645,42 @@ class DeviceRaySampler(object):
         'static_src_cameras': o['static_src_cameras'], 'static_src_masks': None, 'anchor_src_rgbs': o['anchor_src_rgbs'],
         'anchor_src_cameras': o['anchor_src_cameras'], 'selected_inds': select_inds,
     }
+
+
+class FrameRaySampler(object):
+  """``RaySamplerSingleImage``'s contract for one bullet-time frame of a DeviceScene (``bullet_time_plan``): ``.H``, ``.W``, ``.render_stride``,
+  ``.rgb`` and ``get_all()``, with the values of the host sampler on the collated item of ``DynamicVideoDataset.__getitem__``
+  (render_monocular_bt.py:96-259).  ``rgb`` is the stored frame ``gt_frame`` / 255, or None without one."""
+
+  def __init__(self, scene, plan):
+    self.scene, self.plan = scene, plan
+    self.H, self.W = scene.H, scene.W
+    self.device = scene.device
+    self.render_stride = 1
+    self.depth_range = scene.depth_range_f64
+    self._all = None
+
+  def get_all(self):
+    if self._all is None:
+      pl, sc = self.plan, self.scene
+      a, _, c = pl['counts']
+      desc, g = pl['desc'], 0
+      if pl['gt_frame'] is not None:  # the frame's own image is one more view of the same launch
+        g = 1
+        desc = np.concatenate([desc[:a], np.array([[pl['gt_frame'], -1, -1, pl['gt_frame']]], dtype=np.int32), desc[a:]], axis=0)
+      images, cameras, camera, ray_o, ray_d = sc.assemble_frame(desc, (a, g, c), pl['camera'])
+      self._all = {
+          'ray_o': ray_o, 'ray_d': ray_d, 'depth_range': self.depth_range, 'camera': camera, 'render_camera': None, 'anchor_camera': None,
+          'rgb': images[a].reshape(-1, 3) if g else None, 'src_rgbs': images[None, :a], 'src_cameras': cameras[None, :a],
+          'anchor_src_rgbs': None, 'anchor_src_cameras': None, 'static_src_rgbs': images[None, a + g:],
+          'static_src_cameras': cameras[None, a + g:], 'static_src_masks': None, 'disp': None, 'motion_mask': None, 'static_mask': None,
+          'uv_grid': sc.uv_grid(), 'flows': None, 'masks': None,
+      }
+    return dict(self._all)
+
+  @property
+  def rgb(self):
+    return self.get_all()['rgb']  # [H*W, 3] or None
+
+  def random_sample(self, N_rand, sample_mode, center_ratio=0.8):
+    raise NotImplementedError('a bullet-time frame is rendered whole: get_all()')

@@ -730,6 +730,38 @@ typedef struct {
 } DynSceneSupervisionParams;
 int dyn_scene_supervision(const DynSceneStore* s, const DynSceneSupervisionParams* p, void* stream);
 
+/* ====== bullet-time frames from the same resident scene (render_monocular_bt.py:96-259 the item, :342-361 the output stage) ==================
+ *   dyn_scene_views_target  dyn_scene_views for a frame rendered from a camera that is not one of the scene's: a view whose intrinsics
+ *                           frame is -1 takes K from target_camera[2..17] (the script gives a virtual view the RENDER camera's intrinsics,
+ *                           :195-199).  target_camera is a DEVICE [34] array [H, W, K(16), c2w(16)], target_camera_host its host copy for
+ *                           the argument check (H and W must be the store's, every entry finite).  Both NULL: -1 is refused, DYN_E_INVALID,
+ *                           like by dyn_scene_views itself, whose behaviour and output bits are unchanged.  The frame's own image, where a
+ *                           ground truth is wanted, is one more view of the launch; its rays are dyn_image_rays on target_camera.
+ *   dyn_frame_pack_u8       K images (1..4) of fp32 [H,W,3] -> out uint8 [K, H - 2 crop_h, (W - 2 crop_w) * (2 with gt_frame >= 0, else 1), 3]:
+ *                           byte = (uint8)(255.0f * clip(x, 0, 1)), an fp32 multiply and a truncation -- numpy's
+ *                           (255 * np.clip(x, 0, 1)).astype(np.uint8); NaN gives 0 (numpy's cast of NaN is platform-dependent), -inf,
+ *                           negatives and -0.0 give 0, +inf and x > 1 give 255.  With gt_frame >= 0 the LEFT half of every output row is
+ *                           the cropped row of frames + gt_frame * image_stride, copied (the store's bytes are what
+ *                           255 * (float(b) / 255.0f) truncates to, for all 256 values).  Every output byte is written.
+ *                           Refused: K outside 1..4, crops that leave no pixel, a null image or out, H*W*3 >= 2^31, out not on 4 bytes,
+ *                           gt_frame outside -1..N-1 or without frames. */
+int dyn_scene_views_target(const DynSceneStore* s, const int32_t* desc_host, const int32_t* desc, int V_ref, int V_anchor, int V_static,
+                           const float* target_camera_host, const float* target_camera, float* images, float* cameras, void* stream);
+typedef struct {
+  int K, H, W;
+  int crop_h, crop_w;          /* rows / columns dropped at each side */
+  const float* image0;         /* K images [H,W,3]; the rest NULL */
+  const float* image1;
+  const float* image2;
+  const float* image3;
+  int gt_frame;                /* -1: none */
+  int N;                       /* frames of the store (gt_frame >= 0) */
+  const uint8_t* frames;       /* the store's frames and their stride (DynSceneStore), or NULL */
+  long image_stride;
+  uint8_t* out;                /* 4-byte aligned */
+} DynFramePackParams;
+int dyn_frame_pack_u8(const DynFramePackParams* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

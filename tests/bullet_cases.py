@@ -1,0 +1,400 @@
+"""Support for the bullet-time tests (dynibar_amd/scene.py bullet_time_plan / frame_sampler / pack_frames, dynibar_amd/bullet_time.py,
+csrc/dyn_scene.h, csrc/dyn_bullet.h): seeded render cameras that are not in the scene, a numpy restatement of what ``DynamicVideoDataset``
+makes of the synthetic scene's arrays (render_monocular_bt.py:96-259, then ``default_collate`` with batch size 1) and of the script's output
+stage (:342-361), and the checks the device and the emulator tests share.  Test infrastructure: nothing in dynibar_amd imports this.
+
+The restatement reads no files: ``imageio.imread(f)`` is the scene's uint8 array of that frame or virtual view, and
+``cv2.resize(mask, ..., INTER_NEAREST)`` of a mask to the image's own size is the identity.  The two functions of data_utils.py it calls are
+restated here too, independently of dynibar_amd.scene; tests/golden/bullet_plan.npz holds what the real ones return."""
+import functools
+import types
+
+import numpy as np
+import torch
+
+import scene_cases as sc
+
+N_FRAMES = 12  # (with 9 frames, 2 source views and max_range 6 the reference's own rule never finds its 5 static views)
+GOLDEN_INTERVALS = (1, 2, 3, 5)
+GOLDEN_RENDER_POSES = 4
+
+
+def args_of(num_source_views=2, max_range=4, num_vv=0, mask_src_view=False, **more):
+  return types.SimpleNamespace(num_source_views=num_source_views, max_range=max_range, num_vv=num_vv, mask_src_view=mask_src_view, **more)
+
+
+# ---- data_utils.py restated (:85-120 'dist', :123-165 'dist') ---------------------------------------------------------------------------
+def get_nearest_pose_ids(tar_pose, ref_poses):
+  num_cams = len(ref_poses)
+  batched_tar_pose = tar_pose[None, ...].repeat(num_cams, 0)
+  dists = np.linalg.norm(batched_tar_pose[:, :3, 3] - ref_poses[:, :3, 3], axis=1)
+  return np.argsort(dists)
+
+
+def get_interval_pose_ids(tar_pose, ref_poses, interval):
+  original_indices = np.array(range(0, len(ref_poses)))
+  ref_poses = ref_poses[::interval]
+  subsample_indices = original_indices[::interval]
+  return subsample_indices[get_nearest_pose_ids(tar_pose, ref_poses)]
+
+
+# ---- render cameras ---------------------------------------------------------------------------------------------------------------
+def golden_render_poses(name):
+  """[GOLDEN_RENDER_POSES, 4, 4] seeded render poses for sc.golden_poses(name), none of them in the scene, in the scene's dtype.  'ties': the
+  first two sit exactly on lattice points, so that equal distances occur."""
+  rng = np.random.default_rng([{'scattered': 1, 'ties': 2, 'float32': 3, 'long': 4}[name], 78])
+  poses = np.tile(np.eye(4), (GOLDEN_RENDER_POSES, 1, 1))
+  poses[:, :3, 3] = rng.uniform(-1.0, 1.0, (GOLDEN_RENDER_POSES, 3))
+  if name == 'ties':  # the first two lattice points that no camera of the scene occupies
+    taken = {tuple(p) for p in sc.golden_poses(name)[:, :3, 3].tolist()}
+    free = [(x, y, z) for x in (0.0, 1.0, -1.0) for y in (0.0, 1.0, -1.0) for z in (0.0, 1.0, -1.0) if (x, y, z) not in taken]
+    poses[0, :3, 3], poses[1, :3, 3] = free[0], free[1]
+  return poses.astype(np.float32) if name == 'float32' else poses
+
+
+def render_poses(count=4, seed=11):
+  """the render cameras of the tests (the static counts of test_bullet_cpu.STATIC_CASES hold for these four): default_rng(11),
+  synthetic.make_pose(rng, 0.4, 0.05)"""
+  from dynibar_amd import synthetic as syn
+  rng = np.random.default_rng(seed)
+  return np.stack([syn.make_pose(rng, 0.4, 0.05) for _ in range(count)])
+
+
+def render_intrinsics(H, W):
+  """a focal length no frame of the synthetic scene has (theirs lie within 0.78 W (1 +- 0.05)): a virtual view whose camera took a stored
+  frame's intrinsics instead of the render camera's differs"""
+  K = np.eye(4)
+  K[0, 0] = K[1, 1] = 0.9 * W
+  K[0, 2], K[1, 2] = (W - 1) * 0.5 + 0.25, (H - 1) * 0.5 - 0.25
+  return K
+
+
+def host_scene(a):
+  """what bullet_time_plan reads of a DeviceScene (the selection is host work: no device, no library)"""
+  from dynibar_amd import scene as scene_mod
+  s = types.SimpleNamespace(N=a['N'], H=a['H'], W=a['W'], poses_host=a['poses'], virtual_poses_host=a['virtual_poses'],
+                            has_source_masks=a['source_masks'] is not None)
+  s.bullet_time_plan = lambda *x, **k: scene_mod.DeviceScene.bullet_time_plan(s, *x, **k)
+  return s
+
+
+# ---- the reference's item from the same arrays ------------------------------------------------------------------------------------------
+def restate_selection(a, render_pose, render_idx, args):
+  """render_monocular_bt.py:113-153 and :174-183 -> (nearest_pose_ids, static_pose_ids BEFORE the assert of :155, found by the interval pass
+  alone, virtual ids)"""
+  train_poses = a['poses']
+  nearest_pose_ids = np.sort([render_idx + offset for offset in [1, 2, 3, 0, -1, -2, -3]])
+  sp_pose_ids = get_nearest_pose_ids(render_pose, train_poses)
+  static_pose_ids = []
+  frame_interval = args.max_range // args.num_source_views
+  interval_pose_ids = get_interval_pose_ids(render_pose, train_poses, frame_interval)
+  for sp_pose_id in interval_pose_ids:
+    if len(static_pose_ids) >= (args.num_source_views * 2 + 1):
+      break
+    if np.abs(sp_pose_id - render_idx) > (args.max_range + args.num_source_views * 0.5):
+      continue
+    static_pose_ids.append(sp_pose_id)
+  static_pose_set = set(static_pose_ids)
+  by_interval = len(static_pose_ids)
+  for sp_pose_id in sp_pose_ids[::5]:
+    if len(static_pose_ids) >= (args.num_source_views * 2 + 1):
+      break
+    if sp_pose_id in static_pose_set:
+      continue
+    static_pose_ids.append(sp_pose_id)
+  static_pose_ids = np.sort(static_pose_ids)
+  vv_pose_ids = get_nearest_pose_ids(render_pose, a['virtual_poses'][render_idx])
+  return nearest_pose_ids, static_pose_ids, by_interval, vv_pose_ids[:args.num_vv]
+
+
+def restate_item(a, render_pose, intrinsics, render_idx, args, idx=None):
+  """``DynamicVideoDataset.__getitem__(idx)`` (render_monocular_bt.py:96-259) collated with batch size 1.  idx: the loop's index, whose stored frame
+  is the item's ``rgb`` (:105-106); None leaves ``rgb`` out (a path longer than the scene has no such frame)."""
+  from torch.utils.data import default_collate
+  h, w = a['H'], a['W']
+  camera = np.concatenate(([h, w], intrinsics.flatten(), render_pose.flatten())).astype(np.float32)
+  nearest_pose_ids, static_pose_ids, _, virtual_ids = restate_selection(a, render_pose, render_idx, args)
+  assert len(static_pose_ids) == (args.num_source_views * 2 + 1)
+  src_rgbs, src_cameras = [], []
+  for src_idx in nearest_pose_ids:
+    src_rgb = a['images'][src_idx].astype(np.float32) / 255.0
+    src_rgbs.append(src_rgb)
+    src_cameras.append(np.concatenate((list(src_rgb.shape[:2]), a['intrinsics'][src_idx].flatten(), a['poses'][src_idx].flatten())).astype(np.float32))
+  for virtual_idx in virtual_ids:
+    src_rgb = a['virtual_views'][render_idx, virtual_idx].astype(np.float32) / 255.0
+    src_rgbs.append(src_rgb)
+    src_cameras.append(np.concatenate((list(src_rgb.shape[:2]), intrinsics.flatten(), a['virtual_poses'][render_idx, virtual_idx].flatten())).astype(np.float32))
+  src_rgbs, src_cameras = np.stack(src_rgbs, axis=0), np.stack(src_cameras, axis=0)
+  static_src_rgbs, static_src_cameras = [], []
+  for st_near_id in static_pose_ids:
+    src_rgb = a['images'][st_near_id].astype(np.float32) / 255.0
+    if args.mask_src_view:
+      st_mask = a['source_masks'][st_near_id].astype(np.float32) / 255.0
+      if len(st_mask.shape) == 2:
+        st_mask = st_mask[..., None]
+      src_rgb = src_rgb * st_mask
+    static_src_rgbs.append(src_rgb)
+    static_src_cameras.append(
+        np.concatenate((list(src_rgb.shape[:2]), a['intrinsics'][st_near_id].flatten(), a['poses'][st_near_id].flatten())).astype(np.float32))
+  static_src_rgbs, static_src_cameras = np.stack(static_src_rgbs, axis=0), np.stack(static_src_cameras, axis=0)
+  depth_range = torch.tensor([a['depth_range'][0] * 0.9, a['depth_range'][1] * 1.5])
+  item = {
+      'camera': torch.from_numpy(camera), 'rgb_path': '',
+      'src_rgbs': torch.from_numpy(src_rgbs[..., :3]).float(), 'src_cameras': torch.from_numpy(src_cameras).float(),
+      'static_src_rgbs': torch.from_numpy(static_src_rgbs[..., :3]).float(), 'static_src_cameras': torch.from_numpy(static_src_cameras).float(),
+      'depth_range': depth_range, 'ref_time': float(render_idx / float(a['N'])), 'id': render_idx, 'nearest_pose_ids': nearest_pose_ids,
+  }
+  if idx is not None:
+    item['rgb'] = torch.from_numpy(a['images'][idx].astype(np.float32) / 255.0)
+  return default_collate([item])
+
+
+@functools.lru_cache(maxsize=64)
+def planned(H, W, mask_channels, num_vv, render_idx, gt_frame=None, pose=0, num_source_views=2, max_range=4):
+  """(plan, collated data of the restatement) of one frame of the synthetic scene: computed once, shared, not modified"""
+  a = sc.make_scene(H, W, mask_channels, N=N_FRAMES)
+  args = args_of(num_source_views, max_range, num_vv, bool(mask_channels))
+  rp, K = render_poses()[pose], render_intrinsics(H, W)
+  plan = host_scene(a).bullet_time_plan(rp, K, render_idx, args, gt_frame=gt_frame)
+  return plan, restate_item(a, rp, K, render_idx, args, idx=gt_frame)
+
+
+_SCENES = {}
+
+
+def device_scene(device, H, W, mask_channels=0):
+  """DeviceScene.for_rendering of the synthetic scene, uploaded once per test session and device"""
+  from dynibar_amd import scene
+  key = (str(device), H, W, mask_channels)
+  if key not in _SCENES:
+    a = sc.make_scene(H, W, mask_channels, N=N_FRAMES)
+    _SCENES[key] = scene.DeviceScene.for_rendering(device, a['images'], a['intrinsics'], a['poses'], a['depth_range'], a['virtual_views'],
+                                                   a['virtual_poses'], a['source_masks'])
+  return _SCENES[key]
+
+
+def both_samplers(device, H, W, mask_channels, num_vv, render_idx, gt_frame=None):
+  from dynibar_amd import sample_ray
+  plan, data = planned(H, W, mask_channels, num_vv, render_idx, gt_frame)
+  return device_scene(device, H, W, mask_channels).frame_sampler(plan), sample_ray.RaySamplerSingleImage(data, device)
+
+
+# ---- checks ------------------------------------------------------------------------------------------------------------------------------
+def check_get_all(device, H, W, mask_channels, num_vv, gt_frame):
+  """get_all of the frame sampler against the host sampler on the restated item, frames at both ends (render_idx = 3 and N - 4): the same keys,
+  shapes, dtypes and bits; nothing left as the NaN the outputs start with; the virtual views' cameras carry the render intrinsics"""
+  import parity
+  for render_idx in (3, N_FRAMES - 4):
+    tag = f'bullet-time get_all [{H}x{W} masks={mask_channels} vv={num_vv} gt={gt_frame} render_idx={render_idx}]'
+    dev_s, host_s = both_samplers(device, H, W, mask_channels, num_vv, render_idx, gt_frame)
+    assert (dev_s.H, dev_s.W, dev_s.render_stride) == (host_s.H, host_s.W, host_s.render_stride) == (H, W, 1)
+    got, want = dev_s.get_all(), host_s.get_all()
+    sc.assert_same_batch(got, want, tag)
+    assert want['depth_range'].dtype == torch.float64 and tuple(want['depth_range'].shape) == (1, 2)
+    n = 2
+    assert tuple(got['src_rgbs'].shape) == (1, 7 + num_vv, H, W, 3) and tuple(got['static_src_rgbs'].shape) == (1, 2 * n + 1, H, W, 3)
+    assert tuple(got['camera'].shape) == (1, 34)
+    for k, v in got.items():
+      if isinstance(v, torch.Tensor):
+        assert bool(torch.isfinite(v).all()), f'{tag}: {k} has elements the kernels did not write'
+    if gt_frame is None:
+      assert dev_s.rgb is None and host_s.rgb is None
+    else:
+      parity.assert_bitexact(dev_s.rgb, host_s.rgb.to(device), tag + ': .rgb')
+      assert tuple(dev_s.rgb.shape) == (H * W, 3)
+    K = torch.from_numpy(render_intrinsics(H, W).astype(np.float32).reshape(-1)).to(got['src_cameras'].device)
+    a = sc.make_scene(H, W, mask_channels, N=N_FRAMES)
+    for v in range(7 + num_vv):
+      cam_K = got['src_cameras'][0, v, 2:18]
+      assert torch.equal(cam_K, K) == (v >= 7), f'{tag}: view {v} carries the wrong intrinsics'
+      if v < 7:
+        frame = render_idx - 3 + v
+        assert torch.equal(cam_K.cpu(), torch.from_numpy(a['intrinsics'][frame].astype(np.float32).reshape(-1))), f'{tag}: view {v}'
+    try:
+      dev_s.random_sample(4, 'uniform')
+    except NotImplementedError:
+      pass
+    else:
+      raise AssertionError('random_sample of a frame sampler must raise NotImplementedError')
+
+
+def check_views_refusals(device, H=17, W=19):
+  """dyn_scene_views still refuses an intrinsics frame of -1; dyn_scene_views_target refuses it without a camera, and refuses indices out of
+  range, a camera of another size and a camera that is not finite -- on the host, by the library's own check, before anything is launched;
+  a valid call afterwards still gives the right bits.  plan / sampler / assemble of a rendering scene raise ValueError naming the stores."""
+  import ctypes
+  from dynibar_amd import _lib
+  scene = device_scene(device, H, W, 1)
+  plan, _ = planned(H, W, 1, 3, 3)
+  good, counts, cam = plan['desc'], plan['counts'], plan['camera']
+  assert good[7:10, 3].tolist() == [-1, -1, -1] and (good[:7, 3] >= 0).all() and (good[10:, 3] >= 0).all()
+  V = len(good)
+  images = torch.zeros((V, H, W, 3), dtype=torch.float32, device=device)
+  cameras = torch.zeros((V, 34), dtype=torch.float32, device=device)
+  P = lambda t: ctypes.c_void_p(t.data_ptr())
+
+  def refused(fn, match):
+    try:
+      fn()
+    except (ValueError, RuntimeError) as e:
+      assert match in str(e), f'{e!s} does not say {match!r}'
+      assert match.encode() in _lib.lib().dyn_last_error(), _lib.lib().dyn_last_error()
+    else:
+      raise AssertionError(f'a call that must be refused for {match!r} went through')
+
+  def raw(name, desc, camera=None):
+    """the entry point itself, desc / camera given as host arrays and as their device copies"""
+    d_host = torch.from_numpy(np.ascontiguousarray(desc, dtype=np.int32))
+    d_dev = d_host.to(device)
+    extra = ()
+    if name == 'dyn_scene_views_target':
+      if camera is None:
+        extra = (None, None)
+      else:
+        c_host = torch.from_numpy(np.ascontiguousarray(camera, dtype=np.float32))
+        c_dev = c_host.to(device)
+        extra = (P(c_host), P(c_dev))
+    _lib.call(name, ctypes.byref(scene._store), P(d_host), P(d_dev), counts[0], counts[1], counts[2], *extra, P(images), P(cameras),
+              _lib.stream_of(images))
+
+  refused(lambda: raw('dyn_scene_views', good), 'intrinsics frame -1')
+  refused(lambda: raw('dyn_scene_views_target', good), 'no target camera')
+  for row, col, value, match in ((0, 0, N_FRAMES, 'image frame'), (1, 0, -1, 'image frame'), (8, 1, 8, 'virtual index'), (8, 1, -2, 'virtual index'),
+                                 (V - 1, 2, N_FRAMES, 'mask frame'), (2, 3, N_FRAMES, 'intrinsics frame'), (2, 3, -2, 'intrinsics frame')):
+    bad = good.copy()
+    bad[row, col] = value
+    refused(lambda: scene.assemble_frame(bad, counts, cam), match)
+    refused(lambda: raw('dyn_scene_views_target', bad, cam), match)
+  other = cam.copy()
+  other[1] = W + 1
+  refused(lambda: scene.assemble_frame(good, counts, other), 'target camera')
+  other = cam.copy()
+  other[7] = np.inf
+  refused(lambda: scene.assemble_frame(good, counts, other), 'not finite')
+  assert float(images.abs().max()) == 0.0 and float(cameras.abs().max()) == 0.0, 'a refused call wrote'
+  for name, call, stores in (('plan', lambda: scene.plan(0, sc.args_of()), True), ('sampler', lambda: scene.sampler({}), True),
+                             ('assemble', lambda: scene.assemble(good, counts, 3, 4, None), True)):
+    try:
+      call()
+    except ValueError as e:
+      assert 'for_rendering' in str(e) and all(s in str(e) for s in ('disp', 'motion_mask', 'static_mask', 'flows', 'flow_masks')), str(e)
+    else:
+      raise AssertionError(f'{name} of a rendering scene must raise ValueError')
+  check_get_all(device, H, W, 1, 3, 5)
+
+
+# ---- the output stage --------------------------------------------------------------------------------------------------------------------
+def pack_specials():
+  """k / 255 and its two fp32 neighbours for every byte value k, then 0, -0.0, 1, +inf, -inf"""
+  k = (np.arange(256, dtype=np.float32) / np.float32(255.0)).astype(np.float32)
+  s = np.concatenate([np.nextafter(k, np.float32(-1)), k, np.nextafter(k, np.float32(2)),
+                      np.array([0.0, -0.0, 1.0, np.inf, -np.inf], dtype=np.float32)]).astype(np.float32)
+  assert s.dtype == np.float32 and len(s) == 773
+  return s
+
+
+@functools.lru_cache(maxsize=32)
+def pack_inputs(H, W, K, seed=0):
+  """K seeded images [H, W, 3] (read-only): uniform values in [-0.5, 1.5]; at seeded places the special values -- all of them in every image
+  that has twice as many values (35 x 37, 40 x 67), else a window of them that moves on from image to image -- and one NaN per image.
+  -> (images [K, H, W, 3], the flat positions of the NaNs per image)"""
+  rng = np.random.default_rng([seed, H, W, K, 9])
+  n = H * W * 3
+  x = rng.uniform(-0.5, 1.5, (K, n)).astype(np.float32)
+  sp = pack_specials()
+  m = min(len(sp), n // 2)
+  nan_at = []
+  for k in range(K):
+    where = rng.permutation(n)[:m + 1]
+    x[k, where[:m]] = sp[(np.arange(m) + k * m) % len(sp)]
+    x[k, where[m]] = np.nan
+    nan_at.append(int(where[m]))
+  x = x.reshape(K, H, W, 3)
+  x.setflags(write=False)
+  return x, tuple(nan_at)
+
+
+def numpy_pack(x, crop_ratio, gt_u8=None):
+  """render_monocular_bt.py:342-361 for one image [H, W, 3] -> uint8 [h', w' (* 2 with the stored frame gt_u8), 3]"""
+  with np.errstate(invalid='ignore'):
+    pred = (255 * np.clip(x, a_min=0, a_max=1.0)).astype(np.uint8)
+  h, w = pred.shape[:2]
+  crop_h = int(h * crop_ratio)
+  crop_w = int(w * crop_ratio)
+  pred = pred[crop_h:h - crop_h, crop_w:w - crop_w, ...]
+  if gt_u8 is None:
+    return pred
+  gt_rgb = (gt_u8.astype(np.float32) / 255.0)[crop_h:h - crop_h, crop_w:w - crop_w, ...]  # data['rgb'][0, ...] of :356
+  gt_rgb = (255 * np.clip(gt_rgb, a_min=0, a_max=1.)).astype(np.uint8)
+  assert np.array_equal(gt_rgb, gt_u8[crop_h:h - crop_h, crop_w:w - crop_w, ...]), 'the ground-truth half is not a copy of the stored bytes'
+  return np.concatenate([gt_rgb, pred], axis=1)
+
+
+def check_pack(device, H, W, K, gt_frame, crop_ratio=0.03):
+  """pack_frames against the numpy expression byte for byte, the NaN of every image excepted (asserted to give 0); into a fresh tensor and
+  into a poisoned ``out``"""
+  scene = device_scene(device, H, W, 0)
+  a = sc.make_scene(H, W, 0, N=N_FRAMES)
+  x, nan_at = pack_inputs(H, W, K)
+  tag = f'pack_frames [{H}x{W} K={K} gt={gt_frame}]'
+  crop_h, crop_w = int(H * crop_ratio), int(W * crop_ratio)
+  hc, wc = H - 2 * crop_h, W - 2 * crop_w
+  gt = None if gt_frame is None else a['images'][gt_frame]
+  want = np.stack([numpy_pack(x[k], crop_ratio, gt) for k in range(K)])
+  assert want.shape == (K, hc, wc * (2 if gt is not None else 1), 3)
+  compare = np.ones(want.shape, dtype=bool)
+  zeros = []
+  for k, at in enumerate(nan_at):  # the NaN's byte, where the crop keeps it: defined as 0 here, platform-dependent in numpy
+    y, xx, c = np.unravel_index(at, (H, W, 3))
+    if crop_h <= y < H - crop_h and crop_w <= xx < W - crop_w:
+      at_out = (k, y - crop_h, xx - crop_w + (wc if gt is not None else 0), c)
+      compare[at_out] = False
+      zeros.append(at_out)
+  assert compare.size - compare.sum() == len(zeros) <= K
+  images = [torch.from_numpy(x[k].copy()).to(device) for k in range(K)]
+  first = scene.pack_frames(images, crop_ratio, gt_frame)
+  assert first.dtype == torch.uint8 and tuple(first.shape) == want.shape and first.device.type == torch.device(device).type
+  for poison in (0xA5, 0x5A):
+    out = torch.full(want.shape, poison, dtype=torch.uint8, device=device)
+    ret = scene.pack_frames(images, crop_ratio, gt_frame, out=out)
+    assert ret is out
+    for got in (first.cpu().numpy(), out.cpu().numpy()):
+      bad = np.argwhere((got != want) & compare)
+      assert len(bad) == 0, f'{tag}: {len(bad)} bytes differ from numpy, the first at {bad[0]}: {got[tuple(bad[0])]} != {want[tuple(bad[0])]}'
+      for at in zeros:
+        assert got[at] == 0, f'{tag}: NaN must give 0, got {got[at]}'
+
+
+def check_pack_refusals(device, H=16, W=16):
+  from dynibar_amd import _lib
+  scene = device_scene(device, H, W, 0)
+  img = torch.zeros((H, W, 3), dtype=torch.float32, device=device)
+  for call, match in ((lambda: scene.pack_frames([]), '1..4'), (lambda: scene.pack_frames([img] * 5), '1..4'),
+                      (lambda: scene.pack_frames([img], crop_ratio=0.5), 'leaves no pixel'), (lambda: scene.pack_frames([img], crop_ratio=0.7), 'leaves no pixel'),
+                      (lambda: scene.pack_frames([img.double()]), 'float32'), (lambda: scene.pack_frames([img, img[:-1]]), 'like the first'),
+                      (lambda: scene.pack_frames([img], gt_frame=N_FRAMES), 'outside the scene'),
+                      (lambda: scene.pack_frames([img[:, :-1].contiguous()], gt_frame=0), 'stored frames'),
+                      (lambda: scene.pack_frames([img], out=torch.zeros((1, H, W, 3), dtype=torch.float32, device=device)), 'out must be')):
+    try:
+      call()
+    except ValueError as e:
+      assert match in str(e), f'{e!s} does not say {match!r}'
+    else:
+      raise AssertionError(f'pack_frames must refuse ({match})')
+  # the library's own checks, behind the Python ones
+  import ctypes
+  out = torch.zeros((H * W * 3 + 8,), dtype=torch.uint8, device=device)
+  P = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)
+  base = dict(K=1, H=H, W=W, crop_h=0, crop_w=0, image0=P(img), gt_frame=-1, N=N_FRAMES, out=P(out))
+  for over, match in ((dict(K=0), 'K=0'), (dict(K=5), 'K=5'), (dict(crop_h=H // 2), 'leave no pixel'), (dict(crop_w=-1), 'leave no pixel'),
+                      (dict(image0=None), 'image 0 is null'), (dict(K=2), 'image 1 is null'), (dict(out=None), 'out is null'),
+                      (dict(out=P(out, 1)), '4 bytes'), (dict(H=1 << 15, W=1 << 15), 'H*W*3'), (dict(gt_frame=0), 'needs the store'),
+                      (dict(gt_frame=N_FRAMES, frames=P(scene._frames), image_stride=scene._image_stride), 'ground-truth frame')):
+    p = _lib.params('DynFramePackParams', **{**base, **over})
+    try:
+      _lib.call('dyn_frame_pack_u8', ctypes.byref(p), _lib.stream_of(out))
+    except RuntimeError as e:
+      assert match in str(e), f'{e!s} does not say {match!r}'
+    else:
+      raise AssertionError(f'dyn_frame_pack_u8 must refuse ({match})')
+  assert int(out.max()) == 0, 'a refused call wrote'

@@ -1,0 +1,182 @@
+"""The host side of bullet-time rendering from a device-resident scene (dynibar_amd/scene.py bullet_time_plan): its two orderings equal the
+real reference's get_nearest_pose_ids / get_interval_pose_ids (tests/golden/bullet_plan.npz, recorded by tests/golden/make_bullet_golden.py),
+the whole plan equals the restatement of DynamicVideoDataset.__getitem__ in tests/bullet_cases.py for every render_idx, the plan's
+properties, the dtypes of its collated scalars, and the ValueErrors.  No device and no library."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import bullet_cases as bc
+import scene_cases as sc
+from dynibar_amd import scene as scene_mod
+
+# (num_source_views, max_range): on the 12-frame scene the reference's own rule reaches 2 n + 1 static views for all of render_idx 3..8 and the
+# four render poses; (2, 6) and (3, 6) only through the [::5] fill
+STATIC_CASES = [(1, 2), (2, 4), (2, 6), (3, 6)]
+
+
+def test_orderings_equal_the_reference(golden_dir):
+  g = np.load(os.path.join(golden_dir, 'bullet_plan.npz'))
+  assert sorted(g['names'].tolist()) == sorted(sc.GOLDEN_POSES) and tuple(g['intervals'].tolist()) == bc.GOLDEN_INTERVALS
+  for name in sc.GOLDEN_POSES:
+    poses, render = sc.golden_poses(name), bc.golden_render_poses(name)
+    for arr, key in ((poses, 'poses'), (render, 'render_poses')):
+      assert arr.dtype == g[f'{name}/{key}'].dtype and np.array_equal(arr, g[f'{name}/{key}']), f'{name}: the generator drifted from the golden'
+    for r in range(len(render)):
+      assert not any(np.array_equal(render[r], p) for p in poses), 'a render pose must not be one of the scene\'s'
+      for fn, other in ((scene_mod.nearest_pose_ids_dist, bc.get_nearest_pose_ids),):
+        got = fn(render[r], poses, -1)
+        assert got.dtype == g[f'{name}/nearest'].dtype and np.array_equal(got, g[f'{name}/nearest'][r]), f'{name}: render pose {r}'
+        assert np.array_equal(other(render[r], poses), got)
+      for k in bc.GOLDEN_INTERVALS:
+        got = scene_mod.interval_pose_ids_dist(render[r], poses, k)
+        want = g[f'{name}/interval{k}'][r]
+        assert got.dtype == want.dtype and np.array_equal(got, want), f'{name}: render pose {r}, interval {k}'
+        assert np.array_equal(bc.get_interval_pose_ids(render[r], poses, k), want)
+        assert sorted(got.tolist()) == list(range(0, len(poses), k))
+  ties = g['ties/poses'][:, :3, 3]
+  d = np.linalg.norm(g['ties/render_poses'][0, :3, 3] - ties, axis=1)
+  assert len(np.unique(d)) < len(d) - 2, 'the tie case must hold equal distances'
+  assert g['float32/nearest'].dtype == np.int64 and sc.golden_poses('float32').dtype == np.float32
+
+
+@pytest.mark.parametrize('nsv,max_range', STATIC_CASES)
+def test_plan_equals_the_restatement(nsv, max_range):
+  """every render_idx in 3 .. N - 4, four render poses, num_vv 0 / 3 / 8, with and without masks and a ground-truth frame"""
+  a = sc.make_scene(16, 16, 1, N=bc.N_FRAMES)
+  s = bc.host_scene(a)
+  N, H, W = a['N'], a['H'], a['W']
+  K = bc.render_intrinsics(H, W)
+  filled = 0
+  for p, rp in enumerate(bc.render_poses()):
+    for render_idx in range(3, N - 3):
+      num_vv = (0, 3, 8)[(p + render_idx) % 3]
+      mask = bool((p + render_idx) % 2)
+      gt = None if p % 2 else (render_idx + p) % N
+      args = bc.args_of(nsv, max_range, num_vv, mask)
+      near, static, by_interval, virt = bc.restate_selection(a, rp, render_idx, args)
+      # first: the reference's own rule reaches 2 n + 1 here (nothing below is skipped)
+      assert len(static) == 2 * nsv + 1, f'the restated reference finds {len(static)} static views for n={nsv} max_range={max_range} idx={render_idx} pose {p}'
+      filled += by_interval < 2 * nsv + 1
+      plan = s.bullet_time_plan(rp, K, render_idx, args, gt_frame=gt)
+      assert plan['render_idx'] == render_idx and plan['gt_frame'] == gt
+      assert np.array_equal(plan['nearest_pose_ids'], near) and plan['nearest_pose_ids'].tolist() == list(range(render_idx - 3, render_idx + 4))
+      assert np.array_equal(plan['static_pose_ids'], static) and np.array_equal(plan['virtual_ids'], virt)
+      st = plan['static_pose_ids'].tolist()
+      assert st == sorted(st) and len(st) == 2 * nsv + 1 == len(set(st)) and all(0 <= i < N for i in st)
+      vv = plan['virtual_ids'].tolist()
+      assert len(vv) == num_vv == len(set(vv)) and all(0 <= v < 8 for v in vv)
+      assert vv == bc.get_nearest_pose_ids(rp, a['virtual_poses'][render_idx])[:num_vv].tolist()
+      desc, counts = plan['desc'], plan['counts']
+      assert counts == (7 + num_vv, 0, 2 * nsv + 1) and desc.dtype == np.int32 and desc.shape == (sum(counts), 4)
+      assert desc[:7].tolist() == [[i, -1, -1, i] for i in near.tolist()]
+      assert desc[7:7 + num_vv].tolist() == [[render_idx, v, -1, -1] for v in vv]  # the render camera's intrinsics: on virtual views only
+      assert desc[7 + num_vv:].tolist() == [[i, -1, i if mask else -1, i] for i in st]
+      cam = plan['camera']
+      assert cam.dtype == np.float32 and cam.shape == (34,)
+      assert np.array_equal(cam, np.concatenate(([H, W], K.flatten(), rp.flatten())).astype(np.float32))
+      d = plan['data']
+      assert set(d) == {'id', 'ref_time', 'nearest_pose_ids'}
+      assert d['id'].dtype == torch.int64 and d['id'].tolist() == [render_idx]
+      assert d['ref_time'].dtype == torch.float64 and d['ref_time'].tolist() == [render_idx / float(N)]
+      assert d['nearest_pose_ids'].dtype == torch.int64 and d['nearest_pose_ids'].tolist() == [near.tolist()]
+  if (nsv, max_range) in ((2, 6), (3, 6)):
+    assert filled == 4 * (N - 6), 'these cases must need the [::5] fill'
+
+
+def test_plan_data_is_what_collate_makes_of_the_item():
+  for gt in (None, 5):
+    plan, data = bc.planned(16, 16, 1, 3, 4, gt)
+    for k, v in plan['data'].items():
+      assert v.dtype == data[k].dtype and tuple(v.shape) == tuple(data[k].shape) and torch.equal(v, data[k]), k
+    assert torch.equal(torch.from_numpy(plan['camera'])[None], data['camera']) and data['camera'].dtype == torch.float32
+    assert data['depth_range'].dtype == torch.float64 and tuple(data['depth_range'].shape) == (1, 2)
+    assert ('rgb' in data) == (gt is not None)
+
+
+def test_distances_are_computed_in_the_callers_dtype():
+  """a target 2^-26 off the middle between two cameras at -1 and +1: in float32 both distances round to 1 -- a tie, kept in index order --
+  and in float64 the camera at +1 is nearer.  The reference computes in the dtype its poses have; so must the restatement."""
+  for dtype, want in ((np.float32, [0, 1]), (np.float64, [1, 0])):
+    poses = np.tile(np.eye(4, dtype=dtype), (2, 1, 1))
+    poses[0, 0, 3], poses[1, 0, 3] = -1.0, 1.0
+    target = np.eye(4, dtype=dtype)
+    target[0, 3] = 2.0 ** -26
+    assert scene_mod.nearest_pose_ids_dist(target, poses, -1).tolist() == want
+    assert scene_mod.interval_pose_ids_dist(target, poses, 1).tolist() == want
+    assert bc.get_nearest_pose_ids(target, poses).tolist() == want
+
+
+def test_value_errors():
+  a = sc.make_scene(16, 16, 0, N=bc.N_FRAMES)
+  s, rp, K = bc.host_scene(a), bc.render_poses()[0], bc.render_intrinsics(16, 16)
+  plan = lambda idx=5, pose=rp, intr=K, gt=None, **kw: s.bullet_time_plan(pose, intr, idx, bc.args_of(**kw), gt_frame=gt)
+  plan()
+  for idx in (2, -1, bc.N_FRAMES - 3, bc.N_FRAMES):
+    with pytest.raises(ValueError, match=f'render_idx={idx} is outside 3..8'):
+      plan(idx)
+  with pytest.raises(ValueError, match='frame interval of 0'):
+    plan(num_source_views=3, max_range=2)
+  with pytest.raises(ValueError, match='at most 32'):
+    plan(num_source_views=16, max_range=40)
+  with pytest.raises(ValueError, match='num_source_views=0'):
+    plan(num_source_views=0)
+  for num_vv in (-1, 9):
+    with pytest.raises(ValueError, match=f'num_vv={num_vv}'):
+      plan(num_vv=num_vv)
+  with pytest.raises(ValueError, match='without source_masks'):
+    plan(mask_src_view=True)
+  for gt in (-1, bc.N_FRAMES):
+    with pytest.raises(ValueError, match=f'gt_frame={gt} is outside the scene'):
+      plan(gt=gt)
+  with pytest.raises(ValueError, match='render_pose must be'):
+    plan(pose=rp[:3])
+  with pytest.raises(ValueError, match='render_intrinsics must be'):
+    plan(intr=K[:3, :3])
+  with pytest.raises(ValueError, match='numpy array or a torch tensor'):
+    plan(pose=[[0.0] * 4] * 4)
+  # too few static views: 9 frames with 2 source views and max_range 6 never reach 5, by the reference's own rule too (its assert)
+  a9 = sc.make_scene(16, 16, 0, N=9)
+  s9 = bc.host_scene(a9)
+  for p, pose in enumerate(bc.render_poses()):
+    for idx in range(3, 6):
+      args = bc.args_of(2, 6)
+      assert len(bc.restate_selection(a9, pose, idx, args)[1]) < 5
+      with pytest.raises(ValueError, match='static views found'):
+        s9.bullet_time_plan(pose, K, idx, args)
+  with pytest.raises(ValueError, match='empty'):
+    scene_mod.bullet_time_descriptors(5, [], [], [1, 2, 3], False)
+  with pytest.raises(ValueError, match='more than 32'):
+    scene_mod.bullet_time_descriptors(5, [4, 5, 6], [], list(range(12)) * 3, False)
+  # DeviceScene.descriptors keeps refusing an empty list (the bullet-time descriptors are their own function)
+  with pytest.raises(ValueError, match='empty'):
+    scene_mod.DeviceScene.descriptors(s, 3, 4, [4, 5, 6, 2, 1, 0], [], [1, 2], [], [], False)
+
+
+def test_a_rendering_scene_refuses_the_training_calls_by_name():
+  s = bc.host_scene(sc.make_scene(16, 16, 0, N=bc.N_FRAMES))
+  s.missing_stores = scene_mod._TRAINING_STORES
+  for call in (lambda: scene_mod.DeviceScene.plan(s, 0, sc.args_of()), lambda: scene_mod.DeviceScene.sampler(s, {}),
+               lambda: scene_mod.DeviceScene.assemble(s, np.zeros((3, 4), np.int32), (1, 1, 1), 3, 4, None)):
+    with pytest.raises(ValueError, match='for_rendering') as e:
+      call()
+    assert all(k in str(e.value) for k in ('disp', 'motion_mask', 'static_mask', 'flows', 'flow_masks'))
+  a = sc.make_scene(16, 16, 0, N=bc.N_FRAMES)
+  with pytest.raises(ValueError, match='no CPU fallback'):
+    scene_mod.DeviceScene.for_rendering('cpu', a['images'], a['intrinsics'], a['poses'], a['depth_range'], a['virtual_views'], a['virtual_poses'])
+  with pytest.raises(ValueError, match='virtual_poses must be'):
+    scene_mod.DeviceScene.for_rendering('cpu', a['images'], a['intrinsics'], a['poses'], a['depth_range'], a['virtual_views'], a['virtual_poses'][:, :7])
+
+
+def test_the_ground_truth_bytes_survive_the_scripts_round_trip():
+  """(255 * clip(float32(b) / 255, 0, 1)).astype(uint8) == b for all 256 byte values: the ground-truth half is a copy of the stored bytes"""
+  b = np.arange(256, dtype=np.uint8)
+  assert np.array_equal((255 * np.clip(b.astype(np.float32) / 255.0, a_min=0, a_max=1.)).astype(np.uint8), b)
+  x, nan_at = bc.pack_inputs(35, 37, 1)
+  sp = bc.pack_specials()
+  flat = x.reshape(-1)
+  assert np.isnan(flat[nan_at[0]]) and np.isnan(flat).sum() == 1
+  have = set(flat.view(np.int32).tolist())
+  assert all(int(v) in have for v in sp.view(np.int32)), 'an image of 35 x 37 must hold every special value, -0.0 and the infinities included'

@@ -1,0 +1,198 @@
+"""Bullet-time frames from a device-resident scene on the MI355X (dynibar_amd/scene.py, dynibar_amd/bullet_time.py, csrc/dyn_scene.h,
+csrc/dyn_bullet.h) against the existing host path: ``scene.frame_sampler(plan).get_all()`` and ``RaySamplerSingleImage(data, dev).get_all()`` on
+the collated item that tests/bullet_cases.py restates from the same arrays (render_monocular_bt.py:96-259) give the same keys, shapes,
+dtypes and bits, the virtual views' cameras with the render intrinsics; every output element is written (the outputs start as NaN under the
+suite: DYNIBAR_TRAIN_POISON, tests/conftest.py); bad indices and a missing camera are refused before a launch and dyn_scene_views keeps
+refusing -1; the bits do not depend on the call or the stream; a frame costs one asynchronous host-to-device copy and no synchronisation;
+``pack_frames`` equals the script's numpy output stage byte for byte; and one rendered frame goes through ``bullet_time.frames`` to exactly
+the bytes numpy makes of the host path's frame.  Shapes: (5, 7) and (17, 19) make H*W*3 no multiple of 4 (scalar tails, views that do not
+start on 16 bytes), (16, 16) and (18, 32) take the float4 stores; for the output stage (35, 37) crops 1 x 1 and has an odd byte count,
+(40, 67) crops 1 x 2.  An image smaller than the list of special values (5 x 7, 16 x 16) holds a window of it, the larger ones all of it."""
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.utils._python_dispatch
+import torch.utils._pytree
+
+import bullet_cases as bc
+import scene_cases as sc
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+SHAPES = [(16, 16), (17, 19), (5, 7), (18, 32)]
+
+
+@pytest.mark.parametrize('H,W', SHAPES)
+@pytest.mark.parametrize('mask_channels', [0, 1, 3])
+@pytest.mark.parametrize('num_vv', [0, 3])
+@pytest.mark.parametrize('gt_frame', [None, 5])
+def test_get_all_equals_the_host_samplers(H, W, mask_channels, num_vv, gt_frame):
+  """keys, shapes, dtypes and bits, render_idx = 3 and N - 4; complete outputs; the cameras of the virtual views carry the render intrinsics
+  (every stored frame has a focal length of its own and the render camera yet another), those of the temporal views their own frame's"""
+  from dynibar_amd.train_static import POISON_SCRATCH
+  assert POISON_SCRATCH
+  bc.check_get_all(DEV, H, W, mask_channels, num_vv, gt_frame)
+
+
+def test_refusals_and_the_old_entry_point():
+  """dyn_scene_views on a descriptor with -1 is still refused; dyn_scene_views_target without a camera, with indices out of range or with a
+  camera of another size is refused before a launch; a rendering scene refuses plan / sampler / assemble"""
+  bc.check_views_refusals(DEV)
+  torch.cuda.synchronize()
+
+
+def test_bitwise_determinism_across_calls_and_streams():
+  H, W = 18, 32
+  scene = bc.device_scene(DEV, H, W, 3)
+  plan, _ = bc.planned(H, W, 3, 3, 3, 5)
+  other_plan, _ = bc.planned(H, W, 3, 3, bc.N_FRAMES - 4, 5)
+  run = lambda p=plan: scene.frame_sampler(p).get_all()
+  first = run()
+  second = run()
+  torch.cuda.synchronize()
+  side, busy = torch.cuda.Stream(), torch.cuda.Stream()
+  with torch.cuda.stream(side):
+    third = run()
+  torch.cuda.synchronize()
+  with torch.cuda.stream(busy):
+    for _ in range(8):
+      run(other_plan)
+  fourth = run()
+  with torch.cuda.stream(busy):
+    for _ in range(8):
+      run(other_plan)
+  torch.cuda.synchronize()
+  for tag, o in (('second call', second), ('side stream', third), ('beside other frames', fourth)):
+    sc.assert_same_batch(o, first, f'bullet-time frame, {tag}')
+
+
+class _Copies(torch.utils._python_dispatch.TorchDispatchMode):
+  """every aten call that moves tensor data between the host and a device (the counter of tests/test_gpu_scene.py)"""
+
+  def __init__(self):
+    super().__init__()
+    self.h2d, self.d2h = [], []
+
+  def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+    out = func(*args, **(kwargs or {}))
+    flat = torch.utils._pytree.tree_flatten
+    ins = [t for t in flat((args, kwargs or {}))[0] if isinstance(t, torch.Tensor)]
+    outs = [t for t in flat(out)[0] if isinstance(t, torch.Tensor)]
+    on_dev = lambda ts: any(t.device.type == 'cuda' for t in ts)
+    on_host = lambda ts: any(t.device.type == 'cpu' for t in ts)
+    if on_host(ins) and on_dev(outs):
+      self.h2d.append((str(func), [t.numel() * t.element_size() for t in ins if t.device.type == 'cpu']))
+    if on_dev(ins) and (on_host(outs) or 'local_scalar' in str(func)):
+      self.d2h.append(str(func))
+    return out
+
+
+def test_one_copy_and_no_synchronisation():
+  """after a warm-up frame (library load, staging buffers, the pixel grid, allocator growth) a frame's assembly raises nothing under torch's
+  sync debug mode 'error', and torch moves data exactly once: 4 (4 V + 34) bytes from the pinned staging buffer, nothing back"""
+  H, W = 18, 32
+  scene = bc.device_scene(DEV, H, W, 1)
+  plan, data = bc.planned(H, W, 1, 3, 3, 5)
+  from dynibar_amd import sample_ray
+  want = sample_ray.RaySamplerSingleImage(data, DEV).get_all()
+  scene.frame_sampler(plan).get_all()
+  torch.cuda.synchronize()
+  torch.cuda.set_sync_debug_mode('error')
+  try:
+    for _ in range(6):  # (more frames than staging slots: a slot is reused without a wait)
+      got = scene.frame_sampler(plan).get_all()
+  finally:
+    torch.cuda.set_sync_debug_mode('default')
+  sc.assert_same_batch(got, want, 'bullet-time frame under sync debug mode')
+  with _Copies() as seen:
+    scene.frame_sampler(plan).get_all()
+  V = sum(plan['counts']) + 1
+  print('  frame sampler: host-to-device', seen.h2d, 'device-to-host', seen.d2h)
+  assert len(seen.h2d) == 1 and seen.h2d[0][0].startswith('aten.copy_') and seen.h2d[0][1] == [4 * (4 * V + 34)], seen.h2d
+  assert seen.d2h == [], seen.d2h
+  with _Copies() as host_seen:
+    sample_ray.RaySamplerSingleImage(data, DEV).get_all()
+  print(f'  host sampler: {len(host_seen.h2d)} host-to-device copies of {sum(sum(b) for _, b in host_seen.h2d)} bytes')
+  assert len(host_seen.h2d) >= 6  # (the counter sees the copies of the path this one replaces)
+
+
+@pytest.mark.parametrize('H,W', [(5, 7), (16, 16), (35, 37), (40, 67)])
+@pytest.mark.parametrize('K', [1, 3])
+@pytest.mark.parametrize('gt_frame', [None, 7])
+def test_pack_frames_equals_numpy(H, W, K, gt_frame):
+  """byte for byte against (255 * np.clip(x, 0, 1)).astype(np.uint8), crop and concatenation with the stored frame: uniform values in
+  [-0.5, 1.5], k / 255 and its fp32 neighbours, 0, -0.0, 1 and the infinities; one NaN per image gives 0 and is the only byte not compared
+  with numpy; a poisoned ``out`` comes back fully written"""
+  bc.check_pack(DEV, H, W, K, gt_frame)
+
+
+def test_pack_frames_refusals():
+  bc.check_pack_refusals(DEV)
+  torch.cuda.synchronize()
+
+
+# ---- one frame end to end --------------------------------------------------------------------------------------------------------------
+def _dct_basis(K, T):
+  b = np.zeros((T, K), np.float32)
+  for t in range(T):
+    for k in range(1, K + 1):
+      b[t, k - 1] = np.sqrt(2.0 / T) * np.cos(np.pi / (2.0 * T) * (2 * t + 1) * k)
+  return torch.from_numpy(b)
+
+
+def test_one_frame_end_to_end():
+  """16 x 20 (16 is the encoder's minimum), synthetic weights, 7 + 3 + 5 views, 16 samples, three chunks.  The frame rendered from the device
+  sampler (kept on the device) and from the host sampler on the restated item: bit-identical rgb, rgb_static and rgb_dy.  Then
+  bullet_time.frames over two cameras, with and without the stored frame beside the prediction: exactly the bytes numpy makes of the host
+  path's frames."""
+  import cases
+  from dynibar_amd import bullet_time, feature_network, projection, render_image, sample_ray, synthetic as syn
+  H, W, num_vv, render_idx = 16, 20, 3, 5
+  keys = ('rgb', 'rgb_static', 'rgb_dy')
+  a = sc.make_scene(H, W, 1, N=bc.N_FRAMES)
+  scene = bc.device_scene(DEV, H, W, 1)
+  enc = lambda seed: feature_network.ResNet.from_module({k: torch.from_numpy(v).to(DEV) for k, v in syn.make_encoder_weights(seed).items()})
+  model = types.SimpleNamespace(net_coarse_st=syn.make_weights('static', 0), net_coarse_dy=syn.make_weights('dynamic', 0),
+                                motion_mlp=syn.make_weights('motion', 0, num_basis=cases.NUM_BASIS),
+                                trajectory_basis=_dct_basis(cases.NUM_BASIS, cases.NUM_FRAMES).to(DEV), feature_net=enc(0), feature_net_st=enc(1))
+  args = bc.args_of(2, 4, num_vv, True, anti_alias_pooling=0, mask_rgb=1, occ_weights_mode=0, chunk_size=128, N_samples=16, inv_uniform=True,
+                    N_importance=0, white_bkgd=False)
+  projector = projection.Projector(DEV)
+  poses, K = bc.render_poses()[:2], bc.render_intrinsics(H, W)
+
+  def render(sampler, data, render_args):
+    ray_batch = sampler.get_all()
+    with torch.no_grad():
+      cb, _ = model.feature_net(ray_batch['src_rgbs'].squeeze(0).permute(0, 3, 1, 2))
+      st, _ = model.feature_net_st(ray_batch['static_src_rgbs'].squeeze(0).permute(0, 3, 1, 2))
+      idx = int(data['id'].item())
+      offsets = [int(i - idx) for i in data['nearest_pose_ids'].squeeze().tolist()]
+      ret = render_image.render_single_image_mono((idx, None), (data['ref_time'].to(DEV), None), (offsets, None), sampler, ray_batch, model, projector,
+                                                  args.chunk_size, args.N_samples, render_args, inv_uniform=True, N_importance=0, det=True,
+                                                  white_bkgd=False, featmaps=(cb, None, st), is_train=False, num_vv=num_vv)
+    return [ret['outputs_coarse_ref'][k] for k in keys]
+
+  on_device = bc.args_of(**{**vars(args), 'frame_outputs': 'device'})
+  host_frames = []
+  for i, pose in enumerate(poses):
+    data = bc.restate_item(a, pose, K, render_idx, args, idx=i)
+    host = render(sample_ray.RaySamplerSingleImage(data, DEV), data, args)
+    plan = scene.bullet_time_plan(pose, K, render_idx, args, gt_frame=i)
+    device = render(scene.frame_sampler(plan), plan['data'], on_device)
+    for k, h, d in zip(keys, host, device):
+      assert h.device.type == 'cpu' and d.is_cuda and tuple(h.shape) == tuple(d.shape) == (H, W, 3) and d.dtype == torch.float32, k
+      assert torch.equal(h.view(torch.int32), d.cpu().view(torch.int32)), f'camera {i}: {k} differs between the device-fed and the host-fed frame'
+      assert bool(torch.isfinite(h).all())
+    assert float(host[0].std()) > 1e-3, 'the rendered frame must not be flat'
+    host_frames.append([h.numpy() for h in host])
+  for with_gt in (False, True):
+    got = [f.copy() for f in bullet_time.frames(scene, model, projector, args, poses, np.stack([K, K]), render_idx, outputs=keys, with_gt=with_gt)]
+    assert len(got) == 2
+    for i, f in enumerate(got):
+      want = np.stack([bc.numpy_pack(x, 0.03, a['images'][i] if with_gt else None) for x in host_frames[i]])
+      assert f.dtype == np.uint8 and f.shape == want.shape == (3, H, W * (2 if with_gt else 1), 3)
+      assert np.array_equal(f, want), f'camera {i}, with_gt={with_gt}: {int((f != want).sum())} bytes differ from the host path\'s'
+  single = [f.copy() for f in bullet_time.frames(scene, model, projector, args, poses[:1], K[None], render_idx)]
+  assert len(single) == 1 and np.array_equal(single[0], np.stack([bc.numpy_pack(host_frames[0][0], 0.03)]))
