@@ -111,12 +111,14 @@ def _p(t):
 
 
 def frame_sums(pred, target, masks=(), *, data_range, apply_valid=False, valid_as_mask0=False, want_map=False, want_valid=False,
-               want_prepared=False):
+               want_prepared=False, out=None):
   """One ``dyn_frame_metrics`` call on device tensors; no synchronisation, nothing is read back.
 
   pred float32 ``[H, W, 3]``, target float32 or uint8 ``[H, W, 3]``, masks a sequence of float32 ``[H, W, C]`` (or one stacked ``[n, H, W, C]``
   tensor) on pred's device.  -> dict: ``sums`` double ``[M, 3]`` = (sum (a - b)^2 m, sum S m, sum m) per mask, mask 0 being the valid mask when
-  ``valid_as_mask0``; on request ``ssim_map`` double ``[H, W, 3]``, ``valid`` uint8 ``[H, W]``, ``pred`` / ``target`` float32 (the prepared images)."""
+  ``valid_as_mask0``; on request ``ssim_map`` double ``[H, W, 3]``, ``valid`` uint8 ``[H, W]``, ``pred`` / ``target`` float32 (the prepared images).
+  ``out``: a contiguous double ``[M, 3]`` tensor on pred's device (a row block of a larger table, say) that receives the sums and is returned
+  as ``sums``; None allocates one."""
   H, W = int(pred.shape[0]), int(pred.shape[1])
   dev = pred.device
   if isinstance(masks, torch.Tensor):
@@ -134,7 +136,14 @@ def frame_sums(pred, target, masks=(), *, data_range, apply_valid=False, valid_a
   if need == 0:
     raise ValueError(f'frame of {H} x {W} with {M} masks is unsupported (H, W >= 7, H*W*3 < 2^31)')
   ws = _scratch(need // 8, torch.float64, dev)
-  out = dict(sums=_scratch(M * 3, torch.float64, dev).view(M, 3))
+  if out is None:
+    sums = _scratch(M * 3, torch.float64, dev).view(M, 3)
+  elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (M, 3) or not out.is_contiguous()
+        or out.device != dev):
+    raise ValueError(f'out must be a contiguous float64 tensor [{M}, 3] on {dev}')
+  else:
+    sums = out
+  out = dict(sums=sums)
   if want_map:
     out['ssim_map'] = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
   if want_valid:

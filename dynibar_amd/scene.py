@@ -35,7 +35,9 @@ copy, no device-to-host copy and no synchronisation.  There is no CPU fallback: 
 """
 from __future__ import annotations
 
+import collections
 import ctypes
+import os
 import warnings
 
 import numpy as np
@@ -47,6 +49,7 @@ from .train_static import POISON_SCRATCH
 
 MAX_VIEWS = 32       # per source-view list: the network engine's own limit (dyn_scene_views refuses more)
 NUM_VIRTUAL = 8      # virtual views per frame (monocular.py:313)
+NUM_CAMERAS = 12     # cameras of the multi-camera benchmark (eval_nvidia.py:69, :96)
 FLOW_OFFSETS = (1, 2, 3, -1, -2, -3)  # the order of flows / flow_masks along their second axis (monocular.py:216, :249-263)
 _STAGE_SLOTS = 4     # pinned staging buffers in rotation: a slot is rewritten only after the copy that read it has completed
 
@@ -92,7 +95,18 @@ _TRAINING_STORES = ('disp', 'motion_mask', 'static_mask', 'flows', 'flow_masks')
 def _need_training_stores(scene, what):
   missing = getattr(scene, 'missing_stores', ())
   if missing:
-    raise ValueError(f'{what} needs the training stores {", ".join(missing)}: this scene was made by DeviceScene.for_rendering without them')
+    made_by = getattr(scene, 'made_by', 'for_rendering')
+    raise ValueError(f'{what} needs the training stores {", ".join(missing)}: this scene was made by DeviceScene.{made_by} without them')
+
+
+def _need_virtual_views(scene, what):
+  if getattr(scene, 'missing_views', False):
+    raise ValueError(f'{what} needs the virtual views and their poses: this scene was made by DeviceScene.for_evaluation without them')
+
+
+def _need_evaluation(scene, what):
+  if getattr(scene, 'made_by', None) != 'for_evaluation':
+    raise ValueError(f'{what} needs a scene made by DeviceScene.for_evaluation')
 
 
 def nearest_pose_ids_dist(tar_pose, ref_poses, tar_id):
@@ -145,9 +159,36 @@ class DeviceScene(object):
     self._setup(device, images, intrinsics, poses, depth_range, None, virtual_views, virtual_poses, source_masks)
     return self
 
-  def _setup(self, device, images, intrinsics, poses, depth_range, training, virtual_views, virtual_poses, source_masks):
-    """the constructor's checks and uploads; training: (disp, motion_mask, static_mask, flows, flow_masks), or None (for_rendering)"""
+  @classmethod
+  def for_evaluation(cls, device, images, intrinsics, poses, depth_range, coarse_masks=None, gt_views=None, gt_masks=None):
+    """A scene of the 12-camera benchmark for ``eval_step_plan`` / ``eval_view_plan`` / ``eval_sampler`` / ``eval_mask_pair``
+    (``dynibar_amd.nvidia_eval`` is the loop around them; eval_nvidia.py:24-198, :380-457).  It holds no virtual views and no training stores:
+    ``plan``, ``sampler``, ``assemble``, ``bullet_time_plan`` and ``frame_sampler`` raise ValueError on it.
+
+    images        uint8 ``[N, H, W, 3]``, ``N >= 12``; intrinsics, poses ``[N, 4, 4]`` (``batch_parse_llff_poses``)
+    depth_range   ``(near, far)`` as the script has them after :46-48 (15 already added to ``far``).  The item's entry is
+                  ``torch.tensor([near * 0.9, far * 1.5])`` on these very scalars (:184), so its dtype follows theirs: numpy float32 bounds
+                  (``load_llff_data`` casts them) give float32, float64 bounds float64
+    coarse_masks  None, or uint8 ``[N, H, W]``, 0..255 as decoded and resized: a static source view ``id`` with ``3 <= id < N - 3`` is later
+                  multiplied by ``m / 255`` (``args.mask_static``, :156-169, :350-354).  One channel: the script's ``np.ones_like(src_rgb[..., 0])``
+                  fixes ``[H, W]``, a three-channel array is refused
+    gt_views      None, or uint8 ``[N, 12, H, W, 3]``: ``mv_images/%05d/cam%02d.jpg`` after the caller's ``cv2.resize(..., INTER_AREA)`` (:387-392)
+    gt_masks      None, or 0 / 1 as uint8, bool or float32, ``[N, 12, H, W]`` or ``[N, 12, H, W, 3]``:
+                  ``np.float32(cv2.imread(mv_masks...) > 1e-3)`` after the caller's nearest resize (:423-428)
+    Entries of ``gt_views`` / ``gt_masks`` for frames outside ``3 .. N - 4`` are never read.
+
+    Reading and decoding the files and both ``cv2.resize`` modes stay the caller's, once per scene.  cv2, skimage and imageio were not
+    available when this was written, so their semantics are not restated here: the arrays are taken as the caller's own loader produces them."""
+    self = cls.__new__(cls)
+    self._setup(device, images, intrinsics, poses, depth_range, None, None, None, coarse_masks, evaluation=(gt_views, gt_masks))
+    return self
+
+  def _setup(self, device, images, intrinsics, poses, depth_range, training, virtual_views, virtual_poses, source_masks, evaluation=None):
+    """the constructor's checks and uploads; training: (disp, motion_mask, static_mask, flows, flow_masks), or None (for_rendering);
+    evaluation: (gt_views, gt_masks) of for_evaluation, which has no virtual views, else None"""
     self.device = torch.device(device)
+    self.made_by = 'for_evaluation' if evaluation is not None else 'for_rendering' if training is None else '__init__'
+    self.missing_views = evaluation is not None
     images = _np(images, 'images')
     if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
       raise ValueError(f'images must be uint8 [N, H, W, 3], got {images.dtype} {list(images.shape)}')
@@ -156,6 +197,8 @@ class DeviceScene(object):
       raise ValueError(f'a scene needs at least 7 frames (the first and the last 3 are never targets), got {N}')
     if H < 1 or W < 1 or H * W * 3 >= 2 ** 31:
       raise ValueError(f'image size {H} x {W} is unsupported (H*W*3 < 2^31)')
+    if evaluation is not None and N < NUM_CAMERAS:
+      raise ValueError(f'an evaluation scene needs at least {NUM_CAMERAS} frames (one per camera of the benchmark), got {N}')
     self.N, self.H, self.W = N, H, W
     self.intrinsics_host = _shape(_np(intrinsics, 'intrinsics'), (N, 4, 4), 'intrinsics')
     self.poses_host = _shape(_np(poses, 'poses'), (N, 4, 4), 'poses')
@@ -170,12 +213,32 @@ class DeviceScene(object):
       motion_mask = _binary_u8(motion_mask, (N, H, W), 'motion_mask')
       static_mask = _binary_u8(static_mask, (N, H, W), 'static_mask')
       flow_masks = _binary_u8(flow_masks, (N, 6, H, W), 'flow_masks')
-    virtual_views = _shape(_np(virtual_views, 'virtual_views'), (N, NUM_VIRTUAL, H, W, 3), 'virtual_views')
-    if virtual_views.dtype != np.uint8:
-      raise ValueError(f'virtual_views must be uint8, got {virtual_views.dtype}')
-    virtual_poses = _shape(_np(virtual_poses, 'virtual_poses'), (N, NUM_VIRTUAL, 4, 4), 'virtual_poses')
+    if evaluation is None:
+      virtual_views = _shape(_np(virtual_views, 'virtual_views'), (N, NUM_VIRTUAL, H, W, 3), 'virtual_views')
+      if virtual_views.dtype != np.uint8:
+        raise ValueError(f'virtual_views must be uint8, got {virtual_views.dtype}')
+      virtual_poses = _shape(_np(virtual_poses, 'virtual_poses'), (N, NUM_VIRTUAL, 4, 4), 'virtual_poses')
     self.virtual_poses_host = virtual_poses  # as given: bullet_time_plan computes its distances in the caller's dtype
     mask_channels = 1
+    gt_views = gt_masks = None
+    if evaluation is not None:
+      gt_views, gt_masks = evaluation
+      if source_masks is not None:
+        source_masks = _np(source_masks, 'coarse_masks')
+        if tuple(source_masks.shape) != (N, H, W):
+          raise ValueError(f'coarse_masks must be [{N}, {H}, {W}] (one channel: the script builds its own all-ones mask as [H, W]), '
+                           f'got {list(source_masks.shape)}')
+        if source_masks.dtype != np.uint8:
+          raise ValueError(f'coarse_masks must be uint8 (0..255 as decoded), got {source_masks.dtype}')
+      if gt_views is not None:
+        gt_views = _shape(_np(gt_views, 'gt_views'), (N, NUM_CAMERAS, H, W, 3), 'gt_views')
+        if gt_views.dtype != np.uint8:
+          raise ValueError(f'gt_views must be uint8, got {gt_views.dtype}')
+      if gt_masks is not None:
+        gt_masks = _np(gt_masks, 'gt_masks')
+        if tuple(gt_masks.shape) not in ((N, NUM_CAMERAS, H, W), (N, NUM_CAMERAS, H, W, 3)):
+          raise ValueError(f'gt_masks must be [{N}, {NUM_CAMERAS}, {H}, {W}] or [{N}, {NUM_CAMERAS}, {H}, {W}, 3], got {list(gt_masks.shape)}')
+        gt_masks = _binary_u8(gt_masks, gt_masks.shape, 'gt_masks')
     if source_masks is not None:
       source_masks = _np(source_masks, 'source_masks')
       if tuple(source_masks.shape) not in ((N, H, W), (N, H, W, 3)):
@@ -189,16 +252,18 @@ class DeviceScene(object):
     self.depth_range = torch.tensor([[near * 0.9, far * 1.5]]).float().to(self.device)  # [1, 2]: the collated form
     # (the bullet-time item has no .float(), render_monocular_bt.py:245: the script's numpy doubles stay float64 through default_collate)
     self.depth_range_f64 = torch.tensor([[float(near) * 0.9, float(far) * 1.5]], dtype=torch.float64).to(self.device)
+    if evaluation is not None:  # (eval_nvidia.py:184 on the caller's scalars: the dtype is theirs; [1, 2] is the collated form)
+      self.depth_range_eval = torch.tensor([near * 0.9, far * 1.5])[None].to(self.device)
 
     dev = self.device
     self._frames, image_stride = self._padded(images.reshape(N, -1))
-    self._vviews = self._padded(virtual_views.reshape(N * NUM_VIRTUAL, -1))[0]
+    self._vviews = self._padded(virtual_views.reshape(N * NUM_VIRTUAL, -1))[0] if virtual_views is not None else None
     self._src_masks, mask_stride = self._padded(source_masks.reshape(N, -1)) if source_masks is not None else (None, 0)
     f32 = lambda x: _host_tensor(x.astype(np.float32, copy=False)).to(dev)
     u8 = lambda x: _host_tensor(x).to(dev)
     self._intrinsics = f32(self.intrinsics_host.reshape(N, 16))
     self._poses = f32(self.poses_host.reshape(N, 16))
-    self._vposes = f32(virtual_poses.reshape(N, NUM_VIRTUAL, 16))
+    self._vposes = f32(virtual_poses.reshape(N, NUM_VIRTUAL, 16)) if virtual_poses is not None else None
     self._disp = self._flows = self._motion_mask = self._static_mask = self._flow_masks = None
     if training is not None:
       self._disp, self._flows = f32(disp), f32(flows)
@@ -212,6 +277,10 @@ class DeviceScene(object):
                          static_mask=_p(self._static_mask), flows=_p(self._flows), flow_masks=_p(self._flow_masks))
     self._stage_slots = [None] * _STAGE_SLOTS
     self._stage_next = 0
+    if evaluation is not None:
+      self._gt_views = self._padded(gt_views.reshape(N * NUM_CAMERAS, -1))[0] if gt_views is not None else None
+      self._gt_masks = self._padded(gt_masks.reshape(N * NUM_CAMERAS, -1))[0] if gt_masks is not None else None
+      self.gt_mask_channels = 0 if gt_masks is None else 3 if gt_masks.ndim == 5 else 1
 
   def _padded(self, rows):
     """uint8 [n, bytes] -> the device store [n, stride], stride = bytes rounded up to 16 (zero padding), and the stride"""
@@ -389,6 +458,7 @@ class DeviceScene(object):
     ``desc`` (int32 ``[V, 4]`` for dyn_scene_views_target; a virtual view's intrinsics frame is -1: the render camera's, :195-199), ``camera``
     (float32 ``[34]``) and ``data``, the non-image entries of the collated item.  Where the reference asserts or goes wrong silently this raises
     ValueError."""
+    _need_virtual_views(self, 'bullet_time_plan')
     num_frames = int(self.N)
     n = int(args.num_source_views)
     max_range = int(args.max_range)
@@ -450,6 +520,7 @@ class DeviceScene(object):
                 static_pose_ids=static_pose_ids, counts=counts, desc=desc, camera=camera, data=data)
 
   def frame_sampler(self, plan):
+    _need_virtual_views(self, 'frame_sampler')
     return FrameRaySampler(self, plan)
 
   def uv_grid(self):
@@ -544,6 +615,188 @@ class DeviceScene(object):
                **{f'image{i}': _p(t) for i, t in enumerate(images)})
     call('dyn_frame_pack_u8', ctypes.byref(p), stream_of(out))
     return out
+
+
+  # ---- the multi-camera benchmark evaluation (eval_nvidia.py) ---------------------------------------------------------------------------
+  def eval_step_plan(self, render_idx, args):
+    """The source views of one TIME STEP of the evaluation (``DynamicVideoDataset.__getitem__``, eval_nvidia.py:92-119 and :156-169, restated
+    literally): they depend on ``render_idx`` only, not on the target camera.  args: ``mask_static``.  Host work only; reads ``N`` and
+    ``has_source_masks``.
+    -> dict: ``render_idx``, ``mask_static``, ``nearest_pose_ids`` (7, sorted), ``static_pose_ids`` (one frame per other camera, sorted),
+    ``mask_frames`` (per static view: its own id where ``mask_static and 3 <= id < N - 3``, else -1), ``counts`` = (7, Vs), ``desc`` (int32
+    ``[7 + Vs, 4]`` for dyn_scene_views_masked) and ``data``: ``ref_time``, ``id``, ``nearest_pose_ids`` as collated.  Raises ValueError where the
+    script would wrap around with negative indices or run off the end."""
+    num_frames = int(self.N)
+    render_idx = int(render_idx)
+    mask_static = bool(getattr(args, 'mask_static', False))
+    if num_frames < NUM_CAMERAS:
+      raise ValueError(f'an evaluation scene needs at least {NUM_CAMERAS} frames, got {num_frames}')
+    if render_idx < 3 or render_idx > num_frames - 4:
+      raise ValueError(f'render_idx={render_idx} is outside 3..{num_frames - 4}: the temporal views are the frames render_idx - 3 .. render_idx + 3')
+    if mask_static and not self.has_source_masks:
+      raise ValueError('args.mask_static is set but the scene was made without coarse_masks')
+    nearest_pose_ids = np.sort([render_idx + offset for offset in [1, 2, 3, 0, -1, -2, -3]])
+    # 12 is number of viewpoints we sample from input cameras
+    num_imgs_per_cycle = NUM_CAMERAS
+    # the camera viewpoint closest to the target view by index: the benchmark's viewpoints go round-robin
+    static_pose_ids = np.array(list(range(0, num_frames)))
+    static_id_dict = collections.defaultdict(list)
+    for static_pose_id in static_pose_ids:
+      # do not include image with the same viewpoint
+      if static_pose_id % num_imgs_per_cycle == render_idx % num_imgs_per_cycle:
+        continue
+      static_id_dict[static_pose_id % num_imgs_per_cycle].append(static_pose_id)
+    static_pose_ids = []
+    for key in static_id_dict:
+      min_idx = np.argmin(np.abs(np.array(static_id_dict[key]) - render_idx))
+      static_pose_ids.append(static_id_dict[key][min_idx])
+    static_pose_ids = np.sort(static_pose_ids)
+    mask_frames = np.array([int(i) if (mask_static and 3 <= i < num_frames - 3) else -1 for i in static_pose_ids], dtype=np.int64)
+    desc = np.asarray([(int(i), -1, -1, int(i)) for i in nearest_pose_ids] +
+                      [(int(i), -1, int(m), int(i)) for i, m in zip(static_pose_ids, mask_frames)], dtype=np.int32).reshape(-1, 4)
+    counts = (len(nearest_pose_ids), len(static_pose_ids))
+    if counts[1] < 1 or counts[1] > MAX_VIEWS:
+      raise ValueError(f'{counts[1]} static views: 1..{MAX_VIEWS}')
+    data = {  # what default_collate makes of the item's scalars and id list (batch size 1)
+        'id': torch.tensor([render_idx]), 'ref_time': torch.tensor([float(render_idx / float(num_frames))], dtype=torch.float64),
+        'nearest_pose_ids': torch.from_numpy(np.asarray(nearest_pose_ids, dtype=np.int64))[None],
+    }
+    return dict(render_idx=render_idx, mask_static=mask_static, nearest_pose_ids=nearest_pose_ids, static_pose_ids=static_pose_ids,
+                mask_frames=mask_frames, counts=counts, desc=desc, data=data)
+
+  def eval_view_plan(self, step_plan, cam):
+    """The target camera ``cam`` (0..11) of a time step: pose and intrinsics of FRAME ``cam`` (eval_nvidia.py:72-73, ``h, w`` of :80).  Host
+    work only; reads ``H``, ``W``, ``poses_host``, ``intrinsics_host``.
+    -> dict: ``step`` (the step plan), ``cam``, ``render_idx``, ``camera`` (float32 ``[34]``) and ``data``: the step's collated entries and
+    ``rgb_path``, a one-element list with the script's relative tail ``mv_images/%05d/cam%02d.jpg``.  Raises ValueError for a camera outside
+    0..11 and for ``cam == render_idx % 12``, the view the script skips (:317: it has no other-camera ground truth)."""
+    cam = int(cam)
+    render_idx = int(step_plan['render_idx'])
+    if cam < 0 or cam >= NUM_CAMERAS:
+      raise ValueError(f'cam={cam} is outside 0..{NUM_CAMERAS - 1}')
+    if cam == render_idx % NUM_CAMERAS:
+      raise ValueError(f'cam={cam} is the camera of frame render_idx={render_idx} itself ({render_idx} % {NUM_CAMERAS}): the script skips this '
+                       'view, it has no ground truth from another camera')
+    render_pose, intrinsics = self.poses_host[cam], self.intrinsics_host[cam]
+    h, w = int(self.H), int(self.W)
+    camera = np.concatenate(([h, w], intrinsics.flatten(), render_pose.flatten())).astype(np.float32)
+    data = dict(step_plan['data'])
+    data['rgb_path'] = [os.path.join('mv_images', '%05d' % render_idx, 'cam%02d.jpg' % (cam + 1))]
+    return dict(step=step_plan, cam=cam, render_idx=render_idx, camera=camera, data=data)
+
+  def assemble_eval_step(self, step_plan):
+    """The one launch of a time step (dyn_scene_views_masked): both source-view lists, the fp32 masks and, with ``mask_static``, the masked
+    static views the fine encoder is fed (eval_nvidia.py:350-354).  The descriptors go to the device in ONE asynchronous copy from the pinned
+    staging rotation; nothing comes back, nothing synchronises.  -> EvalStep"""
+    _need_evaluation(self, 'assemble_eval_step')
+    H, W, dev = self.H, self.W, self.device
+    desc = np.ascontiguousarray(step_plan['desc'], dtype=np.int32).reshape(-1, 4)
+    a, c = (int(v) for v in step_plan['counts'])
+    V = int(desc.shape[0])
+    if a < 1 or c < 1 or a + c != V:
+      raise ValueError(f'view lists of {(a, c)} for {V} descriptors')
+    if max(a, c) > MAX_VIEWS:
+      raise ValueError(f'{max(a, c)} views in a list: more than {MAX_VIEWS}')
+    masked = bool(step_plan['mask_static'])
+    ref_time = step_plan['data']['ref_time'].numpy().astype(np.float64).reshape(1)
+    n = 4 * V + 2  # the descriptors, then the step's time as the bits of a double (16 V bytes in: on 8 bytes)
+    host, ev, used = self._stage(n)
+    stage = host.numpy()
+    stage[:4 * V] = desc.reshape(-1)
+    stage[4 * V:n] = ref_time.view(np.int32)
+    ints = torch.empty((n,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev) if dev.type == 'cuda' else _Null():
+      ints.copy_(host[:n], non_blocking=True)  # the time step's one host-to-device copy
+      if ev is not None:
+        ev.record()
+        used[0] = True
+    out = self._out
+    src, src_cams = out(a, H, W, 3), out(a, 34)
+    st, st_cams, st_masks = out(c, H, W, 3), out(c, 34), out(c, H, W)  # (allocations of their own: every list starts on 16 bytes)
+    st_masked = out(c, H, W, 3) if masked else None
+    call('dyn_scene_views_masked', ctypes.byref(self._store), ctypes.c_void_p(host.data_ptr()), ctypes.c_void_p(ints.data_ptr()), a, c,
+         1 if masked else 0, _p(src), _p(src_cams), _p(st), _p(st_cams), _p(st_masks), _p(st_masked), stream_of(ints))
+    st = st[None]
+    return EvalStep(step_plan, src[None], src_cams[None], st, st_cams[None], st_masks[None], st_masked[None] if masked else st,
+                    ints[4 * V:].view(torch.float64))
+
+  def _out(self, *shape):
+    t = torch.empty(shape, dtype=torch.float32, device=self.device)
+    if POISON_SCRATCH:  # (train_static.py) under test: every element must be written by the kernels
+      t.fill_(float('nan'))
+    return t
+
+  def eval_sampler(self, step, view_plan):
+    """step: the EvalStep of ``view_plan['step']`` (``assemble_eval_step``), shared by the step's 11 cameras."""
+    _need_evaluation(self, 'eval_sampler')
+    return EvalRaySampler(self, step, view_plan)
+
+  def eval_rays(self, camera):
+    """The per-view part of an evaluation item: camera float32 ``[34]`` -> (camera ``[1, 34]`` on the device, ray_o, ray_d ``[H*W, 3]``).  One
+    pinned asynchronous copy of the 34 floats and the host sampler's own kernel, dyn_image_rays, on the device copy: its bits."""
+    H, W, dev = self.H, self.W, self.device
+    camera = np.ascontiguousarray(camera, dtype=np.float32).reshape(-1)
+    if camera.shape[0] != 34:
+      raise ValueError(f'camera must hold 34 values [H, W, K, c2w], got {camera.shape[0]}')
+    if camera[0] != H or camera[1] != W:
+      raise ValueError(f'the camera is {camera[0]:g} x {camera[1]:g}, the scene\'s images {H} x {W}')
+    host, ev, used = self._stage(34)
+    host.numpy()[:34] = camera.view(np.int32)
+    ints = torch.empty((34,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev) if dev.type == 'cuda' else _Null():
+      ints.copy_(host[:34], non_blocking=True)  # the view's one host-to-device copy
+      if ev is not None:
+        ev.record()
+        used[0] = True
+    ray_o, ray_d = self._out(H * W, 3), self._out(H * W, 3)
+    call('dyn_image_rays', ctypes.c_void_p(ints.data_ptr()), H, W, 1, _p(ray_o), _p(ray_d), stream_of(ints))
+    return ints.view(torch.float32)[None], ray_o, ray_d
+
+  def _gt_index(self, render_idx, cam, what):
+    render_idx, cam = int(render_idx), int(cam)
+    if render_idx < 0 or render_idx >= self.N:
+      raise ValueError(f'{what}: render_idx={render_idx} is outside the scene (0..{self.N - 1})')
+    if cam < 0 or cam >= NUM_CAMERAS:
+      raise ValueError(f'{what}: cam={cam} is outside 0..{NUM_CAMERAS - 1}')
+    return render_idx * NUM_CAMERAS + cam
+
+  def gt_view(self, render_idx, cam):
+    """the stored ground truth of camera ``cam`` at time ``render_idx``: a uint8 ``[H, W, 3]`` view of the store, no copy"""
+    _need_evaluation(self, 'gt_view')
+    if self._gt_views is None:
+      raise ValueError('gt_view: the scene was made without gt_views')
+    return self._gt_views[self._gt_index(render_idx, cam, 'gt_view'), :self.H * self.W * 3].view(self.H, self.W, 3)
+
+  def eval_mask_pair(self, render_idx, cam, out=None):
+    """The stored 0 / 1 dynamic mask of camera ``cam`` at time ``render_idx`` as the fp32 stack ``[2, H, W, C] = (m, 1.0f - m)`` that
+    ``metrics.frame_sums`` takes as its user masks (eval_nvidia.py:423-444): one launch of dyn_eval_mask_pair, every element written.
+    ``out``: a contiguous float32 tensor of that shape to write into."""
+    _need_evaluation(self, 'eval_mask_pair')
+    if self._gt_masks is None:
+      raise ValueError('eval_mask_pair: the scene was made without gt_masks')
+    H, W, C = self.H, self.W, self.gt_mask_channels
+    row = self._gt_masks[self._gt_index(render_idx, cam, 'eval_mask_pair')]
+    shape = (2, H, W, C)
+    if out is None:
+      out = self._out(*shape)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()
+          or out.device != row.device):
+      raise ValueError(f'out must be a contiguous float32 tensor {list(shape)} on {row.device}')
+    call('dyn_eval_mask_pair', _p(row), H, W, C, _p(out), stream_of(out))
+    return out
+
+
+class EvalStep(object):
+  """The tensors of one time step of the evaluation, shared by its 11 target cameras: ``src_rgbs`` ``[1, 7, H, W, 3]``, ``src_cameras``
+  ``[1, 7, 34]``, ``static_src_rgbs`` ``[1, Vs, H, W, 3]``, ``static_src_cameras`` ``[1, Vs, 34]``, ``static_src_masks`` ``[1, Vs, H, W]`` and
+  ``static_src_rgbs_masked``: the product of eval_nvidia.py:350-354, or ``static_src_rgbs`` ITSELF without ``mask_static`` (the script's
+  ``static_src_rgbs_ = static_src_rgbs``).  ``ref_time``: double ``[1]`` on the device, the script's ``data['ref_time'].cuda()``."""
+
+  def __init__(self, plan, src_rgbs, src_cameras, static_src_rgbs, static_src_cameras, static_src_masks, static_src_rgbs_masked, ref_time):
+    self.plan, self.ref_time = plan, ref_time
+    self.src_rgbs, self.src_cameras = src_rgbs, src_cameras
+    self.static_src_rgbs, self.static_src_cameras = static_src_rgbs, static_src_cameras
+    self.static_src_masks, self.static_src_rgbs_masked = static_src_masks, static_src_rgbs_masked
 
 
 def bullet_time_descriptors(render_idx, nearest_pose_ids, virtual_ids, static_pose_ids, mask_src_view):
@@ -684,3 +937,38 @@ class FrameRaySampler(object):
 
   def random_sample(self, N_rand, sample_mode, center_ratio=0.8):
     raise NotImplementedError('a bullet-time frame is rendered whole: get_all()')
+
+
+class EvalRaySampler(object):
+  """``RaySamplerSingleImage``'s contract for one target view of the benchmark evaluation (``eval_view_plan``): ``.H``, ``.W``,
+  ``.render_stride``, ``.rgb_path`` and ``get_all()``, with the values of the host sampler on the collated item of
+  ``DynamicVideoDataset.__getitem__`` (eval_nvidia.py:71-198).  The item has no ``rgb``: that key is None like every other key it lacks.
+  ``static_src_rgbs_masked`` (the step's, :350-354) is an attribute, not a key: the key set stays the reference's."""
+
+  def __init__(self, scene, step, view_plan):
+    if step.plan is not view_plan['step']:
+      raise ValueError('the view plan belongs to another time step than the assembled step')
+    self.scene, self.step, self.plan = scene, step, view_plan
+    self.H, self.W = scene.H, scene.W
+    self.device = scene.device
+    self.render_stride = 1
+    self.depth_range = scene.depth_range_eval
+    self.rgb_path = view_plan['data']['rgb_path']
+    self.static_src_rgbs_masked = step.static_src_rgbs_masked
+    self.rgb = None
+    self._all = None
+
+  def get_all(self):
+    if self._all is None:
+      sc, st = self.scene, self.step
+      camera, ray_o, ray_d = sc.eval_rays(self.plan['camera'])
+      self._all = {
+          'ray_o': ray_o, 'ray_d': ray_d, 'depth_range': self.depth_range, 'camera': camera, 'render_camera': None, 'anchor_camera': None,
+          'rgb': None, 'src_rgbs': st.src_rgbs, 'src_cameras': st.src_cameras, 'anchor_src_rgbs': None, 'anchor_src_cameras': None,
+          'static_src_rgbs': st.static_src_rgbs, 'static_src_cameras': st.static_src_cameras, 'static_src_masks': st.static_src_masks,
+          'disp': None, 'motion_mask': None, 'static_mask': None, 'uv_grid': sc.uv_grid(), 'flows': None, 'masks': None,
+      }
+    return dict(self._all)
+
+  def random_sample(self, N_rand, sample_mode, center_ratio=0.8):
+    raise NotImplementedError('an evaluation view is rendered whole: get_all()')

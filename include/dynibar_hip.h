@@ -762,6 +762,26 @@ typedef struct {
 } DynFramePackParams;
 int dyn_frame_pack_u8(const DynFramePackParams* p, void* stream);
 
+/* ====== a time step of the multi-camera benchmark evaluation from the same resident scene (eval_nvidia.py:121-198, :350-354, :423-444) ======
+ *   dyn_scene_views_masked  the two source-view lists of a TIME STEP (they do not depend on the target camera) in one launch: desc holds
+ *                           V_src + V_static rows of four int32 as for dyn_scene_views (image frame, -1, mask frame or -1, intrinsics frame);
+ *                           only a static view may name a mask frame, and the store's masks must then be one-channel [H,W] (the script's
+ *                           coarse mask).  src_rgbs [V_src,H,W,3] and static_rgbs [V_static,H,W,3] = float(u8) / 255.0f; static_masks
+ *                           [V_static,H,W] = float(m) / 255.0f, or exactly 1.0f for a mask frame of -1; with want_masked = 1 static_masked
+ *                           [V_static,H,W,3] = static_rgbs * static_masks, one fp32 multiply per value (:350-354); with want_masked = 0
+ *                           static_masked must be NULL and nothing is written for it.  src_cameras / static_cameras [.,34].  Each image
+ *                           and mask is fetched once for all of its outputs; every output element is written.
+ *                           Refused before a launch, DYN_E_INVALID: V_src or V_static outside 1..32, a required output that is NULL
+ *                           (static_masked with want_masked), an index out of range, a virtual index other than -1, a mask frame on a
+ *                           temporal view or without a mask store, a three-channel mask store.  The kernel checks the indices again.
+ *   dyn_eval_mask_pair      mask: a stored 0 / 1 mask, uint8 [H,W,C] (C = 1 or 3), 4-byte aligned -> out fp32 [2,H,W,C] = (m, 1.0f - m),
+ *                           m = float(byte), 16-byte aligned: the user masks dyn_frame_metrics takes for the script's dynamic and static
+ *                           numbers (:423-444).  Every output element is written. */
+int dyn_scene_views_masked(const DynSceneStore* s, const int32_t* desc_host, const int32_t* desc, int V_src, int V_static, int want_masked,
+                           float* src_rgbs, float* src_cameras, float* static_rgbs, float* static_cameras, float* static_masks,
+                           float* static_masked, void* stream);
+int dyn_eval_mask_pair(const uint8_t* mask, int H, int W, int C, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,336 @@
+"""Support for the benchmark-evaluation tests (dynibar_amd/scene.py for_evaluation / eval_step_plan / eval_view_plan / eval_sampler /
+eval_mask_pair, dynibar_amd/nvidia_eval.py, csrc/dyn_eval.h): seeded synthetic 12-camera scenes, a numpy restatement of what
+``DynamicVideoDataset.__getitem__`` of eval_nvidia.py (:71-198) makes of such a scene's arrays, independent of dynibar_amd.scene, and the checks
+the device, the emulator and the CPU tests share.  Test infrastructure: nothing in dynibar_amd imports this.
+
+The restatement reads no files: ``imageio.v2.imread(f)`` is the scene's uint8 array of that frame or coarse mask, and
+``cv2.resize(mask, ..., INTER_NEAREST)`` of a mask to the image's own size is the identity.  tests/golden/nvidia_item.npz holds what the real
+``__getitem__`` returns for ``golden_scene`` (tests/golden/make_nvidia_item_golden.py)."""
+import collections
+import ctypes
+import functools
+import os
+import types
+
+import numpy as np
+import torch
+
+NUM_CAMERAS = 12
+GOLDEN_N = (12, 14, 26, 30)
+GOLDEN_CAMS = (0, 5, 11)
+GOLDEN_HW = (6, 8)
+SCENE_PATH = os.path.join('data', 'Balloon1', 'dense')  # the generator's folder_path / scene / 'dense'
+
+
+def args_of(mask_static=False, **more):
+  return types.SimpleNamespace(mask_static=mask_static, **more)
+
+
+def bounds_of(a, dtype):
+  """(near, far) as the script holds them after :46-48, as numpy scalars of ``dtype`` (load_llff_data casts the bounds to float32)"""
+  return dtype(a['bounds'][0]), dtype(a['bounds'][1])
+
+
+# ---- scenes -----------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=8)
+def golden_scene(N):
+  """The 6 x 8 scene of the golden: every frame, mask and camera differs from every other, but with short periods, so that the recorded
+  float32 tensors compress to a few KB.  Coarse masks hold 0, 255 and values between."""
+  H, W = GOLDEN_HW
+  i = np.arange(N)[:, None, None, None]
+  y = np.arange(H)[None, :, None, None]
+  x = np.arange(W)[None, None, :, None]
+  c = np.arange(3)[None, None, None, :]
+  images = ((i * 17 + c * 5 + (x % 2) * 3 + (y % 2) * 64) % 256).astype(np.uint8)
+  coarse = np.array([0, 255, 128, 1], dtype=np.uint8)[(i[..., 0] + x[..., 0] + (y[..., 0] % 2)) % 4]
+  intr = np.tile(np.eye(4), (N, 1, 1))
+  poses = np.tile(np.eye(4), (N, 1, 1))
+  for k in range(N):
+    intr[k, 0, 0] = intr[k, 1, 1] = 8.0 + k
+    intr[k, 0, 2], intr[k, 1, 2] = (W - 1) * 0.5, (H - 1) * 0.5
+    poses[k, 0, 3], poses[k, 1, 3] = 0.25 * k, -0.125 * (k % NUM_CAMERAS)
+  a = dict(N=N, H=H, W=W, images=images, coarse_masks=coarse, intrinsics=intr, poses=poses, bounds=(1.3, 20.7 + 15.0))
+  for v in a.values():
+    if isinstance(v, np.ndarray):
+      v.setflags(write=False)
+  return a
+
+
+@functools.lru_cache(maxsize=16)
+def make_scene(H, W, N=14, gt_mask_channels=3, seed=0):
+  """Seeded arrays as a loader would hold them once per scene (read-only: shared between tests).  Images and coarse masks use every byte
+  value; each frame has its own focal length.  Ground-truth views and 0 / 1 dynamic masks for every frame and camera; the masks of
+  (frame 4, camera 1) are all zero, those of (frame 4, camera 2) all one."""
+  from dynibar_amd import synthetic as syn
+  rng = np.random.default_rng([seed, H, W, N, 12])
+  a = dict(H=H, W=W, N=N)
+  a['images'] = rng.integers(0, 256, (N, H, W, 3), dtype=np.uint8)
+  a['images'][:, 0, 0], a['images'][:, -1, -1] = (0, 255, 1), (254, 0, 255)
+  a['coarse_masks'] = rng.integers(0, 256, (N, H, W), dtype=np.uint8)
+  a['coarse_masks'][:, 0, :2] = np.array([0, 255])
+  intr = np.tile(np.eye(4), (N, 1, 1))
+  for i in range(N):
+    intr[i, 0, 0] = intr[i, 1, 1] = 0.78 * W * rng.uniform(0.95, 1.05)
+    intr[i, 0, 2], intr[i, 1, 2] = (W - 1) * 0.5, (H - 1) * 0.5
+  a['intrinsics'] = intr
+  a['poses'] = np.stack([syn.make_pose(rng, 0.4, 0.05) for _ in range(N)])
+  a['bounds'] = (1.0 + rng.uniform(0, 0.1), 20.0 + rng.uniform(0, 0.1) + 15.0)
+  a['gt_views'] = rng.integers(0, 256, (N, NUM_CAMERAS, H, W, 3), dtype=np.uint8)
+  shape = (N, NUM_CAMERAS, H, W) + ((3,) if gt_mask_channels == 3 else ())
+  a['gt_masks'] = (rng.random(shape) < 0.4).astype(np.float32)
+  a['gt_masks'][4, 1], a['gt_masks'][4, 2] = 0.0, 1.0
+  for v in a.values():
+    if isinstance(v, np.ndarray):
+      v.setflags(write=False)
+  return a
+
+
+def host_scene(a):
+  """what eval_step_plan / eval_view_plan read of a DeviceScene (the selection is host work: no device, no library)"""
+  from dynibar_amd import scene as scene_mod
+  s = types.SimpleNamespace(N=a['N'], H=a['H'], W=a['W'], poses_host=a['poses'], intrinsics_host=a['intrinsics'],
+                            has_source_masks=a.get('coarse_masks') is not None)
+  s.eval_step_plan = lambda *x, **k: scene_mod.DeviceScene.eval_step_plan(s, *x, **k)
+  s.eval_view_plan = lambda *x, **k: scene_mod.DeviceScene.eval_view_plan(s, *x, **k)
+  return s
+
+
+_SCENES = {}
+
+
+def device_scene(device, H, W, N=14, gt_mask_channels=3, bounds_dtype=np.float32, with_masks=True):
+  """DeviceScene.for_evaluation of make_scene(...), uploaded once per test session and device"""
+  from dynibar_amd import scene
+  key = (str(device), H, W, N, gt_mask_channels, bounds_dtype.__name__, with_masks)
+  if key not in _SCENES:
+    a = make_scene(H, W, N, gt_mask_channels)
+    _SCENES[key] = scene.DeviceScene.for_evaluation(device, a['images'], a['intrinsics'], a['poses'], bounds_of(a, bounds_dtype),
+                                                    coarse_masks=a['coarse_masks'] if with_masks else None, gt_views=a['gt_views'],
+                                                    gt_masks=a['gt_masks'])
+  return _SCENES[key]
+
+
+# ---- the reference's item from the same arrays ------------------------------------------------------------------------------------------
+def restate_selection(N, render_idx):
+  """eval_nvidia.py:92-119 -> (nearest_pose_ids, static_pose_ids)"""
+  nearest_pose_ids = np.sort([render_idx + offset for offset in [1, 2, 3, 0, -1, -2, -3]])
+  by_camera = collections.OrderedDict()  # (insertion order, like the script's defaultdict)
+  for i in range(N):
+    if i % NUM_CAMERAS != render_idx % NUM_CAMERAS:
+      by_camera.setdefault(i % NUM_CAMERAS, []).append(i)
+  static_pose_ids = [ids[int(np.argmin(np.abs(np.array(ids) - render_idx)))] for ids in by_camera.values()]  # (a tie: the lower id)
+  return nearest_pose_ids, np.sort(static_pose_ids)
+
+
+def restate_item(a, render_idx, cam, mask_static, bounds):
+  """``DynamicVideoDataset(render_idx, ...).__getitem__(cam)`` (eval_nvidia.py:71-198), not collated.  bounds: (near, far) scalars."""
+  N, h, w = a['N'], a['H'], a['W']
+  camera = np.concatenate(([h, w], a['intrinsics'][cam].flatten(), a['poses'][cam].flatten())).astype(np.float32)
+  nearest_pose_ids, static_pose_ids = restate_selection(N, render_idx)
+
+  def view(i):
+    rgb = a['images'][i].astype(np.float32) / 255.0
+    return rgb, np.concatenate((list(rgb.shape[:2]), a['intrinsics'][i].flatten(), a['poses'][i].flatten())).astype(np.float32)
+
+  src = [view(i) for i in nearest_pose_ids]
+  static = [view(i) for i in static_pose_ids]
+  static_src_masks = []
+  for i in static_pose_ids:
+    if mask_static and 3 <= i < N - 3:
+      static_src_masks.append(a['coarse_masks'][i].astype(np.float32) / 255.0)
+    else:
+      static_src_masks.append(np.ones_like(static[0][0][..., 0]))
+  return {
+      'camera': torch.from_numpy(camera), 'rgb_path': os.path.join(SCENE_PATH, 'mv_images', '%05d' % render_idx, 'cam%02d.jpg' % (cam + 1)),
+      'src_rgbs': torch.from_numpy(np.stack([r for r, _ in src], axis=0)[..., :3]).float(),
+      'src_cameras': torch.from_numpy(np.stack([c for _, c in src], axis=0)).float(),
+      'static_src_rgbs': torch.from_numpy(np.stack([r for r, _ in static], axis=0)[..., :3]).float(),
+      'static_src_cameras': torch.from_numpy(np.stack([c for _, c in static], axis=0)).float(),
+      'static_src_masks': torch.from_numpy(np.stack(static_src_masks, axis=0)).float(),
+      'depth_range': torch.tensor([bounds[0] * 0.9, bounds[1] * 1.5]), 'ref_time': float(render_idx / float(N)), 'id': render_idx,
+      'nearest_pose_ids': nearest_pose_ids,
+  }
+
+
+def collated(item):
+  from torch.utils.data import default_collate
+  return default_collate([item])
+
+
+def golden_cases(N):
+  """(render_idx, cam) of the golden for a scene of N frames: every time step, cameras 0, 5 and 11 except the step's own"""
+  return [(r, c) for r in range(3, N - 3) for c in GOLDEN_CAMS if c != r % NUM_CAMERAS]
+
+
+# ---- checks ------------------------------------------------------------------------------------------------------------------------------
+def check_get_all(device, H, W, N, mask_static, bounds_dtype=np.float32):
+  """get_all of the evaluation sampler against the host sampler on the restated item, at render_idx 3 and N - 4, cameras 0 and 11, both
+  cameras of a step from ONE assembled step: the same keys, shapes, dtypes and bits; nothing left as the NaN the outputs start with; the masked
+  static views are the product bit for bit, or the unmasked tensor itself; the masks of static ids outside 3 .. N - 4 are exactly 1.0"""
+  import scene_cases as sc
+  from dynibar_amd import sample_ray
+  a = make_scene(H, W, N)
+  scene = device_scene(device, H, W, N, bounds_dtype=bounds_dtype)
+  args = args_of(mask_static)
+  bounds = bounds_of(a, bounds_dtype)
+  for render_idx in (3, N - 4):
+    step_plan = scene.eval_step_plan(render_idx, args)
+    step = scene.assemble_eval_step(step_plan)
+    Vs = len(step_plan['static_pose_ids'])
+    assert Vs == NUM_CAMERAS - 1
+    for cam in (0, 11):
+      tag = f'evaluation get_all [{H}x{W} N={N} mask_static={mask_static} render_idx={render_idx} cam={cam}]'
+      view_plan = scene.eval_view_plan(step_plan, cam)
+      dev_s = scene.eval_sampler(step, view_plan)
+      data = collated(restate_item(a, render_idx, cam, mask_static, bounds))
+      host_s = sample_ray.RaySamplerSingleImage(data, device)
+      assert (dev_s.H, dev_s.W, dev_s.render_stride) == (host_s.H, host_s.W, host_s.render_stride) == (H, W, 1)
+      assert dev_s.rgb_path == [os.path.relpath(p, SCENE_PATH) for p in host_s.rgb_path] and dev_s.rgb is None and host_s.rgb is None
+      got, want = dev_s.get_all(), host_s.get_all()
+      sc.assert_same_batch(got, want, tag)
+      assert want['depth_range'].dtype == (torch.float32 if bounds_dtype is np.float32 else torch.float64)
+      assert tuple(got['static_src_masks'].shape) == (1, Vs, H, W) and tuple(got['src_rgbs'].shape) == (1, 7, H, W, 3)
+      assert tuple(got['static_src_rgbs'].shape) == (1, Vs, H, W, 3) and tuple(got['camera'].shape) == (1, 34)
+      for k, v in got.items():
+        if isinstance(v, torch.Tensor):
+          assert bool(torch.isfinite(v).all()), f'{tag}: {k} has elements the kernels did not write'
+      masked = dev_s.static_src_rgbs_masked
+      assert 'static_src_rgbs_masked' not in got
+      if mask_static:
+        # eval_nvidia.py:350-354 on the host sampler's tensors, in the script's layout
+        rgbs = want['static_src_rgbs'].squeeze(0).permute(0, 3, 1, 2)
+        product = rgbs * want['static_src_masks'].squeeze(0)[:, None, ...]
+        mine = masked.squeeze(0).permute(0, 3, 1, 2)
+        assert bool(torch.isfinite(masked).all()), f'{tag}: the masked views have elements the kernel did not write'
+        assert torch.equal(mine.contiguous().view(torch.int32).cpu(), product.contiguous().view(torch.int32).cpu()), f'{tag}: masked views'
+        assert masked is not got['static_src_rgbs']
+      else:
+        assert masked is got['static_src_rgbs'], f'{tag}: without mask_static the masked views are the unmasked tensor itself'
+      outside = [j for j, i in enumerate(step_plan['static_pose_ids']) if not 3 <= i < N - 3]
+      if N == 14 and render_idx == 3:
+        ids = step_plan['static_pose_ids'][outside]
+        assert (ids < 3).any() and (ids >= N - 3).any(), 'this step must select static views at both ends of the scene'
+      for j in outside:
+        assert bool((got['static_src_masks'][0, j] == 1.0).all()), f'{tag}: the mask of static view {j} must be exactly 1'
+      if mask_static:
+        inside = [j for j in range(Vs) if j not in outside]
+        assert inside and any(bool((got['static_src_masks'][0, j] != 1.0).any()) for j in inside)
+      try:
+        dev_s.random_sample(4, 'uniform')
+      except NotImplementedError:
+        pass
+      else:
+        raise AssertionError('random_sample of an evaluation sampler must raise NotImplementedError')
+
+
+def check_mask_pair(device, H, W, C):
+  """eval_mask_pair against numpy: a random 0 / 1 mask, the all-zero and the all-one mask; exact, complete, into a fresh tensor and into ``out``"""
+  N = 14
+  a = make_scene(H, W, N, C)
+  scene = device_scene(device, H, W, N, C)
+  for render_idx, cam in ((3, 0), (4, 1), (4, 2), (N - 4, 11)):
+    m = a['gt_masks'][render_idx, cam].astype(np.float32).reshape(H, W, C)
+    assert {(4, 1): m.max() == 0, (4, 2): m.min() == 1}.get((render_idx, cam), 0 < m.mean() < 1)
+    want = np.stack([m, np.float32(1.0) - m])
+    first = scene.eval_mask_pair(render_idx, cam)
+    out = torch.full((2, H, W, C), 7.0, dtype=torch.float32, device=device)
+    assert scene.eval_mask_pair(render_idx, cam, out=out) is out
+    for got in (first, out):
+      assert got.dtype == torch.float32 and tuple(got.shape) == (2, H, W, C)
+      g = got.cpu().numpy()
+      assert np.isfinite(g).all() and np.array_equal(g.view(np.int32), want.view(np.int32)), f'mask pair [{H}x{W}x{C}] frame {render_idx} cam {cam}'
+
+
+def expect(fn, match, errors=(ValueError,)):
+  try:
+    fn()
+  except errors as e:
+    assert match in str(e), f'{e!s} does not say {match!r}'
+  else:
+    raise AssertionError(f'a call that must be refused for {match!r} went through')
+
+
+def check_entry_refusals(device, H=5, W=7):
+  """Both new entry points refuse before a launch -- DYN_E_INVALID, the cause in dyn_last_error -- and leave their outputs untouched.  The
+  store is built by hand from tensors on ``device``; with 'cpu' and the real library nothing touches a device: every check is host code."""
+  from dynibar_amd import _lib
+  N, V_src, Vs = 12, 7, 11
+  stride = (H * W * 3 + 15) // 16 * 16
+  mstride = (H * W + 15) // 16 * 16
+  frames = torch.zeros((N, stride), dtype=torch.uint8, device=device)
+  masks = torch.zeros((N, mstride), dtype=torch.uint8, device=device)
+  mats = torch.zeros((N, 16), dtype=torch.float32, device=device)
+  P = lambda t, off=0: None if t is None else ctypes.c_void_p(t.data_ptr() + off)
+  store = dict(N=N, H=H, W=W, image_stride=stride, frames=P(frames), src_masks=P(masks), mask_channels=1, mask_stride=mstride,
+               intrinsics=P(mats), poses=P(mats))
+  good = np.array([(i, -1, -1, i) for i in range(V_src)] + [(i, -1, i if 3 <= i < N - 3 else -1, i) for i in range(1, 12)], dtype=np.int32)
+  outs = dict(src_rgbs=(V_src, H, W, 3), src_cameras=(V_src, 34), static_rgbs=(Vs, H, W, 3), static_cameras=(Vs, 34), static_masks=(Vs, H, W),
+              static_masked=(Vs, H, W, 3))
+  outs = {k: torch.zeros(s, dtype=torch.float32, device=device) for k, s in outs.items()}
+
+  def views(desc=good, V_src=V_src, Vs=Vs, want=1, store_over=None, **null):
+    d_host = torch.from_numpy(np.ascontiguousarray(desc, dtype=np.int32))
+    d_dev = d_host.to(device)
+    st = _lib.params('DynSceneStore', **{**store, **(store_over or {})})
+    o = {k: (None if k in null else P(v)) for k, v in outs.items()}
+    _lib.call('dyn_scene_views_masked', ctypes.byref(st), P(d_host), P(d_dev), V_src, Vs, want, o['src_rgbs'], o['src_cameras'], o['static_rgbs'],
+              o['static_cameras'], o['static_masks'], o['static_masked'], _lib.stream_of(outs['src_rgbs']))
+
+  def refused(fn, match):
+    expect(fn, match, (RuntimeError,))
+    assert match.encode() in _lib.lib().dyn_last_error(), _lib.lib().dyn_last_error()
+
+  def bad(row, col, value):
+    d = good.copy()
+    d[row, col] = value
+    return d
+
+  refused(lambda: views(Vs=0), '0 static views')
+  refused(lambda: views(Vs=33), '33 static views')
+  refused(lambda: views(V_src=0), '0 temporal views')
+  refused(lambda: views(static_masks=None), 'are required')
+  refused(lambda: views(src_rgbs=None), 'are required')
+  refused(lambda: views(static_masked=None), 'static_masked is null')
+  refused(lambda: views(want=0), 'were not asked for')
+  refused(lambda: views(bad(0, 0, N)), 'image frame')
+  refused(lambda: views(bad(9, 0, -1)), 'image frame')
+  refused(lambda: views(bad(9, 1, 0)), 'virtual index')
+  refused(lambda: views(bad(9, 2, N)), 'mask frame')
+  refused(lambda: views(bad(2, 2, 4)), 'temporal view')
+  refused(lambda: views(bad(9, 3, -1)), 'intrinsics frame')
+  refused(lambda: views(store_over=dict(src_masks=None, mask_stride=0)), 'the store has none')
+  refused(lambda: views(store_over=dict(mask_channels=3, mask_stride=stride)), 'one channel')
+  refused(lambda: views(store_over=dict(frames=None)), 'frames, intrinsics and poses')
+
+  mask = torch.zeros((mstride,), dtype=torch.uint8, device=device)
+  pair = torch.zeros((2 * H * W * 3 + 8,), dtype=torch.float32, device=device)
+  mp = lambda m=P(mask), h=H, w=W, c=1, o=P(pair): _lib.call('dyn_eval_mask_pair', m, h, w, c, o, _lib.stream_of(pair))
+  refused(lambda: mp(c=2), 'C=2')
+  refused(lambda: mp(m=None), 'mask is null')
+  refused(lambda: mp(o=None), 'out is null')
+  refused(lambda: mp(m=P(mask, 1)), '4 bytes')
+  refused(lambda: mp(o=P(pair, 4)), '16 bytes')
+  refused(lambda: mp(h=0), 'H=0')
+  refused(lambda: mp(h=1 << 15, w=1 << 15), 'H*W*3')
+  for k, t in list(outs.items()) + [('pair', pair)]:
+    assert float(t.abs().max()) == 0.0, f'a refused call wrote {k}'
+
+
+def check_scene_refusals(scene):
+  """plan / sampler / assemble / bullet_time_plan / frame_sampler on an evaluation scene (or a stand-in with its attributes) raise ValueError
+  and name what is missing and who made the scene"""
+  from dynibar_amd import scene as scene_mod
+  import scene_cases as sc
+  D = scene_mod.DeviceScene
+  eye = np.eye(4)
+  for name, fn, words in (('plan', lambda: D.plan(scene, 0, sc.args_of()), ('disp', 'flows', 'for_evaluation')),
+                          ('sampler', lambda: D.sampler(scene, {}), ('disp', 'flows', 'for_evaluation')),
+                          ('assemble', lambda: D.assemble(scene, np.zeros((3, 4), np.int32), (1, 1, 1), 3, 4, None), ('disp', 'for_evaluation')),
+                          ('bullet_time_plan', lambda: D.bullet_time_plan(scene, eye, eye, 3, sc.args_of()), ('virtual views', 'for_evaluation')),
+                          ('frame_sampler', lambda: D.frame_sampler(scene, {}), ('virtual views', 'for_evaluation'))):
+    try:
+      fn()
+    except ValueError as e:
+      assert name in str(e) and all(w in str(e) for w in words), f'{name}: {e!s}'
+    else:
+      raise AssertionError(f'{name} of an evaluation scene must raise ValueError')

@@ -1,0 +1,171 @@
+"""The host side of the benchmark evaluation from a device-resident scene (dynibar_amd/scene.py for_evaluation / eval_step_plan /
+eval_view_plan): the numpy restatement of eval_nvidia.py's ``DynamicVideoDataset.__getitem__`` in tests/eval_scene_cases.py equals what the
+REAL class returned (tests/golden/nvidia_item.npz, recorded by tests/golden/make_nvidia_item_golden.py) on every entry and dtype; the two
+plans equal the golden's ids, mask flags, cameras, depth ranges (both dtypes), times and paths for every recorded case; and every refusal of
+the scene, the plans and the two entry points raises with a message that names the cause.  No device is touched."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import eval_scene_cases as ec
+from dynibar_amd import scene as scene_mod
+
+TENSORS = ('src_rgbs', 'src_cameras', 'static_src_rgbs', 'static_src_cameras', 'static_src_masks')
+
+
+@pytest.fixture(scope='module')
+def golden(golden_dir):
+  g = np.load(os.path.join(golden_dir, 'nvidia_item.npz'))
+  assert tuple(g['N'].tolist()) == ec.GOLDEN_N and tuple(g['cams'].tolist()) == ec.GOLDEN_CAMS and str(g['scene_path']) == ec.SCENE_PATH
+  return g
+
+
+def _same(got, want, what):
+  assert got.dtype == want.dtype and got.shape == want.shape, f'{what}: {got.dtype} {got.shape}, the reference gives {want.dtype} {want.shape}'
+  view = np.int32 if got.dtype == np.float32 else np.int64
+  assert np.array_equal(got.view(view), want.view(view)), f'{what} differs from the reference'
+
+
+@pytest.mark.parametrize('N', ec.GOLDEN_N)
+def test_the_restatement_equals_the_reference(golden, N):
+  g, a = golden, ec.golden_scene(N)
+  steps = g[f'N{N}/steps'].tolist()
+  assert steps == list(range(3, N - 3))
+  cases = [tuple(c) for c in g[f'N{N}/cases'].tolist()]
+  assert cases == ec.golden_cases(N)
+  for dtype in (np.float32, np.float64):
+    want_depth = g[f'N{N}/depth_range/{dtype.__name__}']
+    assert want_depth.dtype == dtype
+    for mask_static in (False, True):
+      for k, (render_idx, cam) in enumerate(cases):
+        item = ec.restate_item(a, render_idx, cam, mask_static, ec.bounds_of(a, dtype))
+        s, tag = steps.index(render_idx), f'N={N} render_idx={render_idx} cam={cam} mask_static={mask_static}'
+        assert set(item) == set(TENSORS) | {'camera', 'rgb_path', 'depth_range', 'ref_time', 'id', 'nearest_pose_ids'}
+        for key in TENSORS:
+          _same(item[key].numpy(), g[f'N{N}/mask{int(mask_static)}/{key}'][s], f'{tag}: {key}')
+        _same(item['camera'].numpy(), g[f'N{N}/camera'][k], f'{tag}: camera')
+        _same(item['depth_range'].numpy(), want_depth, f'{tag}: depth_range')
+        _same(np.asarray(item['nearest_pose_ids']), g[f'N{N}/mask{int(mask_static)}/nearest_pose_ids'][s], f'{tag}: nearest_pose_ids')
+        assert item['rgb_path'] == str(g[f'N{N}/rgb_path'][k]) and type(item['ref_time']) is float and type(item['id']) is int
+        assert item['ref_time'] == float(g[f'N{N}/mask{int(mask_static)}/ref_time'][s]) and item['id'] == int(g[f'N{N}/mask{int(mask_static)}/id'][s])
+        assert np.array_equal(ec.restate_selection(N, render_idx)[1], g[f'N{N}/mask{int(mask_static)}/static_ids'][s])
+  masks = g[f'N{N}/mask1/static_src_masks']
+  assert (g[f'N{N}/mask0/static_src_masks'] == 1.0).all() and (masks != 1.0).any()
+
+
+@pytest.mark.parametrize('N', ec.GOLDEN_N)
+def test_the_plans_equal_the_reference(golden, N):
+  g, a = golden, ec.golden_scene(N)
+  s = ec.host_scene(a)
+  steps = g[f'N{N}/steps'].tolist()
+  cases = [tuple(c) for c in g[f'N{N}/cases'].tolist()]
+  ties = 0
+  for mask_static in (False, True):
+    m = int(mask_static)
+    for i, render_idx in enumerate(steps):
+      plan = s.eval_step_plan(render_idx, ec.args_of(mask_static))
+      tag = f'N={N} render_idx={render_idx} mask_static={mask_static}'
+      near, static = g[f'N{N}/mask{m}/nearest_pose_ids'][i], g[f'N{N}/mask{m}/static_ids'][i]
+      assert np.array_equal(plan['nearest_pose_ids'], near) and np.array_equal(plan['static_pose_ids'], static), tag
+      assert plan['counts'] == (7, 11) and plan['mask_static'] is mask_static and plan['render_idx'] == render_idx
+      # the mask rule, read off the reference's masks: a view without a coarse mask is all ones
+      masked = [bool((x != 1.0).any()) for x in g[f'N{N}/mask{m}/static_src_masks'][i]]
+      assert [f >= 0 for f in plan['mask_frames']] == masked, tag
+      assert all(f in (-1, i_) for f, i_ in zip(plan['mask_frames'], static))
+      desc = plan['desc']
+      assert desc.dtype == np.int32 and desc.shape == (18, 4)
+      assert np.array_equal(desc[:, 0], np.concatenate([near, static])) and (desc[:, 1] == -1).all() and np.array_equal(desc[:, 3], desc[:, 0])
+      assert (desc[:7, 2] == -1).all() and np.array_equal(desc[7:, 2], plan['mask_frames'])
+      # the descriptors name the frames whose cameras the reference stacked (every frame of the golden scene has a focal length of its own)
+      focal = np.concatenate([g[f'N{N}/mask{m}/src_cameras'][i][:, 2], g[f'N{N}/mask{m}/static_src_cameras'][i][:, 2]])
+      assert np.array_equal(a['intrinsics'][desc[:, 3], 0, 0].astype(np.float32), focal), tag
+      d = plan['data']
+      assert d['ref_time'].dtype == torch.float64 and tuple(d['ref_time'].shape) == (1,) and float(d['ref_time']) == float(g[f'N{N}/mask{m}/ref_time'][i])
+      assert d['id'].dtype == torch.int64 and d['id'].tolist() == [int(g[f'N{N}/mask{m}/id'][i])]
+      assert d['nearest_pose_ids'].dtype == torch.int64 and tuple(d['nearest_pose_ids'].shape) == (1, 7)
+      assert d['nearest_pose_ids'][0].tolist() == near.tolist()
+      lower = [c for c in static if abs(c - render_idx) == abs(c + ec.NUM_CAMERAS - render_idx) and c + ec.NUM_CAMERAS < N]
+      ties += len(lower)
+      for cam in ec.GOLDEN_CAMS:
+        if (render_idx, cam) not in cases:
+          with pytest.raises(ValueError, match='the script skips this'):
+            s.eval_view_plan(plan, cam)
+          continue
+        k = cases.index((render_idx, cam))
+        vp = s.eval_view_plan(plan, cam)
+        _same(vp['camera'], g[f'N{N}/camera'][k], f'{tag} cam={cam}: camera')
+        assert vp['camera'].shape == (34,) and vp['step'] is plan and vp['cam'] == cam
+        path = vp['data']['rgb_path']
+        assert isinstance(path, list) and len(path) == 1 and os.path.join(ec.SCENE_PATH, path[0]) == str(g[f'N{N}/rgb_path'][k])
+        assert vp['data']['ref_time'] is d['ref_time'] and vp['data']['nearest_pose_ids'] is d['nearest_pose_ids']
+  if N >= 26:
+    assert ties > 0, 'a scene of two cycles must hold a tie between two frames of a camera: it goes to the lower id'
+
+
+@pytest.mark.parametrize('N', (12, 14))
+def test_depth_range_follows_the_callers_scalars(golden, N):
+  """torch.tensor([near * 0.9, far * 1.5]) on float32 and float64 bounds is what the reference's item holds, collated to [1, 2]"""
+  a = ec.golden_scene(N)
+  for dtype in (np.float32, np.float64):
+    near, far = ec.bounds_of(a, dtype)
+    t = torch.tensor([near * 0.9, far * 1.5])[None]
+    _same(t[0].numpy(), golden[f'N{N}/depth_range/{dtype.__name__}'], 'depth_range')
+    assert tuple(ec.collated(ec.restate_item(a, 3, 0, False, (near, far)))['depth_range'].shape) == (1, 2)
+
+
+def test_scene_refusals_name_the_cause():
+  a = ec.make_scene(5, 7, 12, 3)
+  D = scene_mod.DeviceScene
+  base = dict(images=a['images'], intrinsics=a['intrinsics'], poses=a['poses'], depth_range=a['bounds'], coarse_masks=a['coarse_masks'],
+              gt_views=a['gt_views'], gt_masks=a['gt_masks'])
+  make = lambda device='cuda:0', **over: D.for_evaluation(device, **{**base, **over})
+  three = np.repeat(a['coarse_masks'][..., None], 3, axis=-1)
+  not_binary = a['gt_masks'].copy()
+  not_binary[3, 0, 0, 0] = 0.5
+  for over, match in ((dict(images=a['images'][:11], intrinsics=a['intrinsics'][:11], poses=a['poses'][:11]), 'at least 12 frames'),
+                      (dict(images=a['images'].astype(np.float32)), 'images must be uint8'),
+                      (dict(poses=a['poses'][:, :3]), 'poses must be'),
+                      (dict(coarse_masks=three), 'one channel'),
+                      (dict(coarse_masks=a['coarse_masks'][:, :-1]), 'coarse_masks must be'),
+                      (dict(coarse_masks=a['coarse_masks'].astype(np.float32)), 'coarse_masks must be uint8'),
+                      (dict(gt_views=a['gt_views'][:, :11]), 'gt_views must be'),
+                      (dict(gt_views=a['gt_views'].astype(np.float32)), 'gt_views must be uint8'),
+                      (dict(gt_masks=a['gt_masks'][:, :, :-1]), 'gt_masks must be'),
+                      (dict(gt_masks=a['gt_masks'].astype(np.float64)), 'uint8, bool or float32'),
+                      (dict(gt_masks=not_binary), 'only 0 and 1'),
+                      (dict(device='cpu'), 'needs a HIP device')):  # (valid arguments on the host: there is no CPU fallback)
+    ec.expect(lambda: make(**over), match)
+  stand_in = ec.host_scene(a)
+  stand_in.missing_stores, stand_in.missing_views, stand_in.made_by = scene_mod._TRAINING_STORES, True, 'for_evaluation'
+  ec.check_scene_refusals(stand_in)
+  rendering = ec.host_scene(a)  # a scene that was not made by for_evaluation refuses the evaluation's device calls
+  rendering.made_by = 'for_rendering'
+  for name, fn in (('assemble_eval_step', lambda: D.assemble_eval_step(rendering, {})), ('eval_sampler', lambda: D.eval_sampler(rendering, None, {})),
+                   ('eval_mask_pair', lambda: D.eval_mask_pair(rendering, 3, 0)), ('gt_view', lambda: D.gt_view(rendering, 3, 0))):
+    ec.expect(fn, 'for_evaluation')
+
+
+def test_plan_refusals_name_the_cause():
+  a = ec.make_scene(5, 7, 14, 3)
+  s = ec.host_scene(a)
+  N = a['N']
+  for render_idx in (2, -1, N - 3, N):
+    ec.expect(lambda: s.eval_step_plan(render_idx, ec.args_of()), f'render_idx={render_idx} is outside 3..{N - 4}')
+  bare = ec.host_scene({**a, 'coarse_masks': None})
+  ec.expect(lambda: bare.eval_step_plan(3, ec.args_of(True)), 'without coarse_masks')
+  assert bare.eval_step_plan(3, ec.args_of(False))['mask_frames'].tolist() == [-1] * 11
+  plan = s.eval_step_plan(5, ec.args_of(True))
+  for cam in (-1, 12):
+    ec.expect(lambda: s.eval_view_plan(plan, cam), 'outside 0..11')
+  ec.expect(lambda: s.eval_view_plan(plan, 5), 'the script skips this view')
+  ec.expect(lambda: s.eval_view_plan(s.eval_step_plan(N - 4, ec.args_of()), (N - 4) % 12), 'the script skips this view')
+  short = ec.host_scene({**a, 'N': 11})
+  ec.expect(lambda: short.eval_step_plan(3, ec.args_of()), 'at least 12 frames')
+
+
+def test_entry_point_refusals_need_no_device():
+  """dyn_scene_views_masked and dyn_eval_mask_pair check their arguments in host code before anything is launched: with host buffers and no
+  device every refusal comes back as DYN_E_INVALID with its message, and nothing is written"""
+  ec.check_entry_refusals('cpu')
