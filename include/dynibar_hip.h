@@ -782,6 +782,55 @@ int dyn_scene_views_masked(const DynSceneStore* s, const int32_t* desc_host, con
                            float* static_masked, void* stream);
 int dyn_eval_mask_pair(const uint8_t* mask, int H, int W, int C, float* out, void* stream);
 
+/* ====== the view panels the training loop logs (train.py:576-762 log_view_to_tb; utils.py:97-170 colorize; flow_utils.py:17-153) ============
+ * Three launches turn the device-resident groups of a rendered frame into the values the script hands to its summary writer; nothing
+ * goes through the host in between.  All images are H x W, n = H*W, H*W*3 < 2^31.  Inputs are never written (the script's flow_to_image
+ * zeroes unknown pixels in its argument; these do not).  Inputs must be finite.
+ *   dyn_viewlog_ranges    for K scalar images (1..4): ranges [K][2] (DEVICE doubles) = (vmin, vmax) of colorize without mask or range,
+ *                         np.percentile(x, (1, 99)) by the `linear` method in numpy's arithmetic, vmax += 1e-6.  Image k is image[k], fp32
+ *                         [H,W], or with magnitude[k] set it is formed from image[k] as fp32 [H,W,3] by sqrtf(fmaf(z, z, fmaf(y, y, x * x)))
+ *                         -- torch.norm(dim=-1) on the host, bit for bit -- and also written to mag_out[k], fp32 [H,W] (required then).
+ *                         The host passes what depends on n alone: rank[4] = the indices (0..n-1) of the order statistics below and
+ *                         above the 1st and the 99th percentile, weight[2] = numpy's interpolation weights (doubles).  Per percentile
+ *                         a, b = the two order statistics, d = fp32(b - a), then a + d t in double, or b - d (1 - t) where t >= 0.5.
+ *                         One workgroup per image selects the four order statistics exactly: a radix select in three passes of 11 / 11 /
+ *                         10 bits over the order-preserving integer key of the float (-0.0 counts as +0.0), integer LDS histograms only.
+ *   dyn_viewlog_flow_max  for F flow images (1..12), fp32 [H,W,2]: maxrad [F] (DEVICE fp32) = max(-1, max sqrtf(u*u + v*v)) in fp32 over
+ *                         the pixels, a pixel with |u| > 200 or |v| > 200 counting as (0, 0).  An integer maximum of the bits of
+ *                         non-negative floats: independent of the order.
+ *   dyn_viewlog_panels    one grid over every output element.
+ *                         rgb panels (0..8): fp32 [H,W,3] -> fp32 [3,H,W], with rgb_clamp[i] clamped to 0..1 (torch.clamp).
+ *                         map panels (0..4): x fp32 [H,W] and its (vmin, vmax) from ranges -> double [3,H,W] (map_chw) or [H,W,3]: in
+ *                         double, clip(x, vmin, vmax), (x - vmin) / (vmax - vmin), clip(0, 1), index min(int(x * 256), 255) into
+ *                         map_table[i], 256 x 3 DEVICE doubles.
+ *                         flow panels (0..12): fp32 [H,W,2] and its maxrad -> [H,W,3], the Middlebury colour code of flow_to_image
+ *                         in double from the divisor maxrad + 2^-52 on; flow_u8: the uint8 image, else fp32(double(byte) / 255.0).
+ * rank, weight and the pointer lists (image, magnitude, mag_out, flow, rgb_src, ...) are HOST arrays; what they point to is on the device.
+ * Refused before a launch, DYN_E_INVALID: counts outside the limits, a null pointer in a list, H or W below 1, H*W*3 >= 2^31, a rank
+ * outside 0..n-1, a weight outside 0..1 (n = 1 passes 1.0), pointers that are not aligned to their element. */
+int dyn_viewlog_ranges(int K, int H, int W, const void* image, const int32_t* magnitude, const void* mag_out, const int32_t* rank,
+                       const double* weight, double* ranges, void* stream);
+int dyn_viewlog_flow_max(int F, int H, int W, const void* flow, float* maxrad, void* stream);
+typedef struct {
+  int H, W;
+  int n_rgb;                   /* 0..8 */
+  const void* rgb_src;         /* HOST list of n_rgb DEVICE pointers, fp32 [H,W,3] */
+  const int32_t* rgb_clamp;    /* HOST [n_rgb] 0 / 1 */
+  const void* rgb_dst;         /* HOST list of n_rgb DEVICE pointers, fp32 [3,H,W] */
+  int n_map;                   /* 0..4 */
+  const void* map_src;         /* HOST list of n_map DEVICE pointers, fp32 [H,W] */
+  const void* map_table;       /* HOST list of n_map DEVICE pointers, double [256,3] */
+  const double* ranges;        /* DEVICE [n_map][2] (dyn_viewlog_ranges) */
+  const void* map_dst;         /* HOST list of n_map DEVICE pointers, double [3,H,W] or [H,W,3] */
+  int map_chw;
+  int n_flow;                  /* 0..12 */
+  const void* flow_src;        /* HOST list of n_flow DEVICE pointers, fp32 [H,W,2] */
+  const float* maxrad;         /* DEVICE [n_flow] (dyn_viewlog_flow_max) */
+  const void* flow_dst;        /* HOST list of n_flow DEVICE pointers, fp32 or uint8 [H,W,3] */
+  int flow_u8;
+} DynViewLogPanelsParams;
+int dyn_viewlog_panels(const DynViewLogPanelsParams* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
