@@ -35,7 +35,7 @@ enum DynKernelSlot {
   DYN_K_TRAIN_GEMM, DYN_K_TRAIN_ROWS, DYN_K_TRAIN_ATTN, DYN_K_TRAIN_GATHER_BWD, DYN_K_MOTION_TAIL, DYN_K_STATIC_PLAN,
   DYN_K_SPLAT_PROJECT, DYN_K_SPLAT_KEYS, DYN_K_SPLAT_SORT, DYN_K_SPLAT_RESOLVE, DYN_K_SOBEL_ALPHA, DYN_K_VV_FINISH,
   DYN_K_OBJECTIVE_FWD, DYN_K_OBJECTIVE_BWD, DYN_K_METRICS_TILE, DYN_K_METRICS_FINISH,
-  DYN_K_SCENE_VIEWS, DYN_K_SCENE_SUPERVISION, DYN_K_FRAME_PACK, DYN_K_SCENE_VIEWS_MASKED, DYN_K_EVAL_MASK_PAIR,
+  DYN_K_SCENE_VIEWS, DYN_K_SCENE_SUPERVISION, DYN_K_FRAME_PACK, DYN_K_SCENE_VIEWS_MASKED, DYN_K_EVAL_MASK_PAIR, DYN_K_ADAM_STEP,
   DYN_K_VIEWLOG_RANGES, DYN_K_VIEWLOG_FLOW_MAX, DYN_K_VIEWLOG_PANELS, DYN_K_COUNT
 };
 void dyn_prof_begin(int slot, hipStream_t stream);

@@ -831,6 +831,37 @@ typedef struct {
 } DynViewLogPanelsParams;
 int dyn_viewlog_panels(const DynViewLogPanelsParams* p, void* stream);
 
+/* ====== the optimizer step of the training loop (train.py:199, :467 model.optimizer.step(); ibrnet/model.py:341-364 torch.optim.Adam) =========
+ * ONE launch updates every tensor of every parameter group.  The grid is a list of chunks of DYN_ADAM_CHUNK elements: chunk c is elements
+ * chunks[c][1] * DYN_ADAM_CHUNK ... of tensor chunks[c][0]; the list depends on the sizes alone and is uploaded once per parameter set.  The
+ * per-tensor records change with every step (the gradient's address, the scalars that depend on the tensor's own step count and on the
+ * group's learning rate) and are uploaded by the caller before the launch, on the same stream.
+ * Per element, fp32, every operation rounded once (no fma), division and square root correctly rounded, subnormals kept:
+ *     m = m + c1 * (g - m)          v = v * beta2 + (c2 * g) * g          denom = sqrtf(v) / s2 + eps          p = p + (a * m) / denom
+ * with c1 = fp32(1 - beta1), c2 = fp32(1 - beta2), s2 = fp32(sqrt(1 - beta2^t)), a = fp32(-lr / (1 - beta1^t)), t the tensor's step count
+ * after its increment, all formed by the host in double and rounded once.  A record with skip != 0 (a parameter without a gradient) is
+ * left alone: p, g, m, v are not read.  With zero_grads the kernel stores 0 to g after reading it.  A chunk whose four pointers are all
+ * 16-byte aligned at its first element moves float4s, any other chunk single floats; n < 2^31 per tensor.
+ * Refused before a launch, DYN_E_INVALID: null params, records or chunks, counts below 1, records not on 8 bytes, chunks not on 8 bytes.
+ * The kernel leaves a chunk alone whose tensor index or first element lies outside the records. */
+#define DYN_ADAM_CHUNK 4096
+typedef struct {
+  float *p, *g, *m, *v;        /* DEVICE fp32 [n]: parameter, gradient, first and second moment, 4-byte aligned */
+  int64_t n;                   /* elements, 1 .. 2^31 - 1 */
+  float a, s2;                 /* depend on the step count and the learning rate */
+  float c1, c2, beta2, eps;    /* depend on the group's options */
+  int32_t skip;                /* 1: no gradient this step, the tensor is not touched */
+  int32_t reserved;
+} DynAdamTensor;
+typedef struct {
+  const void* tensors;         /* DEVICE [n_tensors] DynAdamTensor, 8-byte aligned */
+  int n_tensors;
+  const int32_t* chunks;       /* DEVICE [n_chunks][2]: tensor index, chunk index within the tensor; 8-byte aligned */
+  int n_chunks;
+  int zero_grads;              /* 0 / 1 */
+} DynAdamParams;
+int dyn_adam_step(const DynAdamParams* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,150 @@
+"""The optimizer step on the kid-running model's parameter set: dynibar_amd.optim.Adam (one k_adam_step launch) against torch.optim.Adam, in one
+process on the same gradients.  GPU only -- there is no CPU path.
+
+  python tools/optimbench.py [--rounds 30] [--inner 20] [--out profiles/optimizer.txt]
+
+The parameter set is the model's (ibrnet/model.py:341-364): the static and the dynamic MLP, the motion MLP (shapes of dynibar_amd.synthetic's layer
+tables), the two ResNet encoders (its encoder weights) and the trajectory basis, in the reference's six groups with its four learning rates
+(configs/train_kid-running.txt: lrate_mlp 4e-4, lrate_feature 8e-4), with seeded random gradients.  One step of this optimizer is first compared
+with the numpy restatement of the contract (tests/optim_cases.py), exactly.  Then four legs alternate after a warm-up, each on its own copy of the
+parameters: (1) this optimizer, (2) torch.optim.Adam with its default implementation, (3) the same again -- the spread between two identical
+legs --, (4) torch.optim.Adam(foreach=False), the per-tensor loop the reference's torch ran.  A leg is `inner` steps timed by the host clock
+around work that ends in a stream synchronise.  In a separate pass the kernel's own time comes from the library's events, and with it the
+bytes the kernel moves (16 read and 12 written per element) over that time.  The loop leaves the ~30 MB working set in the 256 MiB Infinity
+Cache between steps; in training the rest of the iteration passes through the cache in between.  No ratio is fixed in advance."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+LRATE_MLP, LRATE_FEATURE = 4e-4, 8e-4
+
+
+def parameter_set():
+  """[(lr, [numpy float32 arrays])]: the six groups of model.py:341-364 in its order"""
+  import numpy as np
+  from dynibar_amd import synthetic as syn
+  import train_case
+  basis = np.random.default_rng(5).standard_normal((train_case.NUM_FRAMES, train_case.NUM_BASIS)).astype(np.float32)
+  return [(LRATE_MLP * 0.5, list(syn.make_weights('static', 0).values())),
+          (LRATE_FEATURE * 0.5, list(syn.make_encoder_weights(1).values())),
+          (LRATE_MLP, list(syn.make_weights('dynamic', 0).values())),
+          (LRATE_FEATURE, list(syn.make_encoder_weights(0).values())),
+          (LRATE_MLP, list(syn.make_weights('motion', 0, num_basis=train_case.NUM_BASIS).values())),
+          (LRATE_MLP * 0.25, [basis])]
+
+
+def run(rounds, inner, dev='cuda:0'):
+  import numpy as np
+  import torch
+  import optim_cases as oc
+  from dynibar_amd import _lib, optim
+  groups = parameter_set()
+  rng = np.random.default_rng(31)
+  host_grads = [[oc.gradient(rng, a.size).reshape(a.shape) for a in arrs] for _, arrs in groups]
+  grads = [[torch.from_numpy(g).to(dev) for g in gs] for gs in host_grads]
+
+  def make(cls, **kw):
+    ps = [[torch.nn.Parameter(torch.from_numpy(a.copy()).to(dev)) for a in arrs] for _, arrs in groups]
+    for pg, gg in zip(ps, grads):
+      for p, g in zip(pg, gg):
+        p.grad = g
+    return ps, cls([{'params': pg if i < 5 else pg[0], 'lr': lr} for i, ((lr, _), pg) in enumerate(zip(groups, ps))], **kw)
+
+  # one step against the restatement, exactly
+  ps, opt = make(optim.Adam)
+  opt.step()
+  torch.cuda.synchronize()
+  for (lr, arrs), pg, gs in zip(groups, ps, host_grads):
+    for a, p, g in zip(arrs, pg, gs):
+      n = a.size
+      wp, wm, wv = oc.restate(a.reshape(-1), g.reshape(-1), np.zeros(n, np.float32), np.zeros(n, np.float32), lr, 0.9, 0.999, 1e-8, 1)
+      oc.same(wp, p, 'p')
+      oc.same(wm, opt.state[p]['exp_avg'], 'm')
+      oc.same(wv, opt.state[p]['exp_avg_sq'], 'v')
+
+  legs = [('hip', make(optim.Adam)[1]), ('torch_default', make(torch.optim.Adam)[1]), ('torch_default_again', make(torch.optim.Adam)[1]),
+          ('torch_foreach_false', make(torch.optim.Adam, foreach=False)[1])]
+  times = {name: [] for name, _ in legs}
+  for r in range(rounds + 2):
+    for name, o in legs:
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      for _ in range(inner):
+        o.step()
+      torch.cuda.synchronize()
+      if r >= 2:
+        times[name].append((time.perf_counter() - t0) * 1e3 / inner)
+  # the fused clearing against step + zero_grad(set_to_none=False), each on gradients of its own
+  pz, oz = make(optim.Adam)
+  for pg in pz:
+    for p in pg:
+      p.grad = p.grad.clone()
+  clear = {'hip_step_zero_grads': [], 'hip_step_then_zero_grad': []}
+  for r in range(rounds + 2):
+    for name in clear:
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      for _ in range(inner):
+        if name == 'hip_step_zero_grads':
+          oz.step(zero_grads=True)
+          oz.zero_grad(set_to_none=False)
+        else:
+          oz.step()
+          oz.zero_grad(set_to_none=False)
+      torch.cuda.synchronize()
+      if r >= 2:
+        clear[name].append((time.perf_counter() - t0) * 1e3 / inner)
+  # the kernel's own time
+  lib = _lib.lib()
+  nk = lib.dyn_profile_count()
+  ms, cnt = np.zeros(nk, np.float32), np.zeros(nk, np.int32)
+  hip = legs[0][1]
+  lib.dyn_profile_enable(1)
+  lib.dyn_profile_read(ms.ctypes.data, cnt.ctypes.data)
+  for _ in range(rounds * inner):
+    hip.step()
+  torch.cuda.synchronize()
+  lib.dyn_profile_read(ms.ctypes.data, cnt.ctypes.data)
+  lib.dyn_profile_enable(0)
+  kern = {lib.dyn_profile_name(i).decode(): (float(ms[i]) / int(cnt[i]), int(cnt[i])) for i in range(nk) if cnt[i]}
+  assert list(kern) == ['k_adam_step'] and kern['k_adam_step'][1] == rounds * inner, kern
+  kernel_ms = kern['k_adam_step'][0]
+  elements = sum(a.size for _, arrs in groups for a in arrs)
+  tensors = sum(len(arrs) for _, arrs in groups)
+  moved = 28 * elements
+  q = lambda v: dict(median=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4))
+  res = {name: q(v) for name, v in times.items()}
+  med = {name: statistics.median(v) for name, v in times.items()}
+  spread = abs(med['torch_default'] - med['torch_default_again'])
+  return dict(tensors=tensors, elements=elements, groups=len(groups), chunks=hip._tables['n_chunks'], chunk=optim.CHUNK, rounds=rounds, inner=inner,
+              step_ms=res, clearing_ms={k: q(v) for k, v in clear.items()}, torch_default_spread_ms=round(spread, 4),
+              hip_minus_torch_default_ms=round(med['hip'] - min(med['torch_default'], med['torch_default_again']), 4),
+              hip_no_slower_than_torch_default=bool(med['hip'] <= max(med['torch_default'], med['torch_default_again']) + spread),
+              kernel_ms=round(kernel_ms, 5), kernel_bytes=moved, kernel_tb_per_s=round(moved / (kernel_ms * 1e-3) / 1e12, 3),
+              share_of_8_tb_per_s=round(moved / (kernel_ms * 1e-3) / 8e12, 3), exact=True, device=torch.cuda.get_device_name(0), torch=torch.__version__)
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--rounds', type=int, default=30)
+  ap.add_argument('--inner', type=int, default=20)
+  ap.add_argument('--out', default=None)
+  a = ap.parse_args()
+  line = json.dumps(run(a.rounds, a.inner))
+  print(line)
+  if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+      f.write(line + '\n')
+
+
+if __name__ == '__main__':
+  main()

@@ -1,7 +1,8 @@
 """The reference's two training stages on synthetic data, end to end on this package (train.py:116-199 static bootstrap, :203-467 main loop):
 seeded scene and targets, the reference's optimizer setup (Adam over the three MLPs' parameters + the trajectory basis, model.py:339-378),
 `render_rays_mono` under grad mode, the script's loss, `loss.backward()` through the HIP training kernels, `optimizer.step()`.
-Prints the loss every few iterations; the losses must go down.     python tools/train_loop.py [iterations] [rays]
+Prints the loss every few iterations; the losses must go down.     python tools/train_loop.py [iterations] [rays] [--encoders] [--optimizer hip|torch]
+--optimizer hip steps with dynibar_amd.optim.Adam (one HIP launch per step) instead of torch.optim.Adam, the default.
 """
 import json
 import os
@@ -34,9 +35,11 @@ def main_loss(ret, batch):
   return loss + 0.05 * torch.mean(torch.abs(anc['sf_seq']))
 
 
-def run(dev='cuda:0', iters=40, R=1024, S=64, log_every=10, quiet=False, encoders=False):
+def run(dev='cuda:0', iters=40, R=1024, S=64, log_every=10, quiet=False, encoders=False, optimizer='torch'):
   """encoders: also train feature_net / feature_net_st (train.py:272-281: the maps are recomputed from the source images every iteration by
   the encoder's training form, the gradients of the maps flow on into its parameters, which sit in the optimizer with lrate_feature)."""
+  if optimizer not in ('hip', 'torch'):
+    raise ValueError(f'unknown optimizer {optimizer!r}: hip or torch')
   tc = TrainCase(dev, R=R, S=S)
   g = torch.Generator().manual_seed(9)
   batch = dict(tc.batch)
@@ -51,7 +54,11 @@ def run(dev='cuda:0', iters=40, R=1024, S=64, log_every=10, quiet=False, encoder
     from dynibar_amd import synthetic as syn, train_encoder
     enc = [{k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in syn.make_encoder_weights(sd).items() if k in train_encoder.PARAMS} for sd in (0, 1)]
     groups.append({'params': [p for e in enc for p in e.values()], 'lr': 1e-3})  # lrate_feature
-  opt = torch.optim.Adam(groups)
+  if optimizer == 'hip':
+    from dynibar_amd import optim
+    opt = optim.Adam(groups)
+  else:
+    opt = torch.optim.Adam(groups)
   hist = {'bootstrap': [], 'main': []}
   for stage in ('bootstrap', 'main'):
     t0 = time.perf_counter()
@@ -83,6 +90,13 @@ def run(dev='cuda:0', iters=40, R=1024, S=64, log_every=10, quiet=False, encoder
 
 
 if __name__ == '__main__':
-  it = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-  R = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
-  print(json.dumps(run(iters=it, R=R, encoders='--encoders' in sys.argv)))
+  argv = list(sys.argv[1:])
+  which = 'torch'
+  if '--optimizer' in argv:
+    k = argv.index('--optimizer')
+    which = argv[k + 1]
+    del argv[k:k + 2]
+  pos = [a for a in argv if not a.startswith('--')]
+  it = int(pos[0]) if len(pos) > 0 else 40
+  R = int(pos[1]) if len(pos) > 1 else 1024
+  print(json.dumps(run(iters=it, R=R, encoders='--encoders' in argv, optimizer=which)))
