@@ -39,7 +39,9 @@ static const char* const g_prof_names[DYN_K_COUNT] = {
     "k_train_gemm", "k_train_rows", "k_train_attn", "k_gather_bwd", "k_motion_zero_tail", "k_ragged_plan",
     "k_splat_project", "k_splat_keys", "k_splat_sort", "k_splat_resolve", "k_sobel_alpha", "k_vv_finish",
     "k_objective_fwd", "k_objective_bwd", "k_metrics_tile", "k_metrics_finish", "k_scene_views", "k_scene_supervision", "k_frame_pack_u8",
-    "k_scene_views_masked", "k_eval_mask_pair", "k_adam_step", "k_viewlog_ranges", "k_viewlog_flow_max", "k_viewlog_panels"};
+    "k_scene_views_masked", "k_eval_mask_pair", "k_adam_step",
+    "k_resize_area_u8", "k_resize_linear_f32", "k_resize_nearest", "k_erode_disk_u8", "k_percentile_pair",
+    "k_viewlog_ranges", "k_viewlog_flow_max", "k_viewlog_panels"};
 
 static void prof_flush(int slot) {
   for (int i = 0; i < g_prof.used[slot]; ++i) {
@@ -1943,4 +1945,5 @@ extern "C" int dyn_plucker_src(const float* pts, int per_view_pts, const float* 
 #include "dyn_bullet.h"
 #include "dyn_eval.h"
 #include "dyn_viewlog.h"
+#include "dyn_ingest.h"
 #include "dyn_optim.h"

@@ -88,28 +88,16 @@ __device__ __forceinline__ void vl_for_each_key(const float* x, long n, F f) {
   }
 }
 
-// grid: K workgroups, block VL_THREADS, LDS VL_RANGES_LDS
-__global__ __launch_bounds__(VL_THREADS) void k_viewlog_ranges(VlRangesArgs a) {
-  unsigned* hist = reinterpret_cast<unsigned*>(dyn_smem);  // [4][VL_BINS]
-  unsigned* wtot = hist + 4 * VL_BINS;                      // [16] counts of the wavefronts' bins
-  unsigned* sel = wtot + 16;                                // [4] the key bits found so far, [4] the rank among the keys that share them
-  const int img = blockIdx.x, tid = threadIdx.x, lane = dyn_lane(), wave = dyn_wave();
-  const long n = a.n;
-  const float* x = a.image[img];
-  if (a.magnitude[img]) {
-    float* m = a.mag_out[img];
-    for (long i = tid; i < n; i += VL_THREADS) {
-      const float vx = x[3 * i], vy = x[3 * i + 1], vz = x[3 * i + 2];
-      m[i] = sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx)));
-    }
-    __syncthreads();  // the passes below read what other threads of this workgroup wrote
-    x = m;
-  }
+// The radix select of one workgroup of VL_THREADS: the keys of the four order statistics rank[0..3] of x[0..n) end up in sel[0..3] (read them after
+// a __syncthreads()).  hist [4][VL_BINS], wtot [16] counts of the wavefronts' bins, sel [4] the key bits found so far + [4] the rank among the
+// keys that share them: LDS.
+__device__ __forceinline__ void vl_select4(const float* x, long n, const unsigned (&rank)[4], unsigned* hist, unsigned* wtot, unsigned* sel) {
+  const int tid = threadIdx.x, lane = dyn_lane(), wave = dyn_wave();
   const int g = tid >> 8, t = tid & 255;  // the scan: 256 threads per rank, bins 8 t .. 8 t + 7
   for (int pass = 0; pass < 3; ++pass) {
     for (int i = tid; i < 4 * VL_BINS; i += VL_THREADS) hist[i] = 0u;
     __syncthreads();
-    unsigned p0 = 0u, p1 = 0u, p2 = 0u, p3 = 0u, my_prefix = 0u, my_rank = a.rank[g];
+    unsigned p0 = 0u, p1 = 0u, p2 = 0u, p3 = 0u, my_prefix = 0u, my_rank = rank[g];
     if (pass > 0) {
       p0 = sel[0]; p1 = sel[1]; p2 = sel[2]; p3 = sel[3];
       my_prefix = sel[g];
@@ -161,6 +149,26 @@ __global__ __launch_bounds__(VL_THREADS) void k_viewlog_ranges(VlRangesArgs a) {
       sel[4 + g] = rem;
     }
   }
+}
+
+// grid: K workgroups, block VL_THREADS, LDS VL_RANGES_LDS
+__global__ __launch_bounds__(VL_THREADS) void k_viewlog_ranges(VlRangesArgs a) {
+  unsigned* hist = reinterpret_cast<unsigned*>(dyn_smem);  // [4][VL_BINS]
+  unsigned* wtot = hist + 4 * VL_BINS;                      // [16] counts of the wavefronts' bins
+  unsigned* sel = wtot + 16;                                // [4] the key bits found so far, [4] the rank among the keys that share them
+  const int img = blockIdx.x, tid = threadIdx.x;
+  const long n = a.n;
+  const float* x = a.image[img];
+  if (a.magnitude[img]) {
+    float* m = a.mag_out[img];
+    for (long i = tid; i < n; i += VL_THREADS) {
+      const float vx = x[3 * i], vy = x[3 * i + 1], vz = x[3 * i + 2];
+      m[i] = sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx)));
+    }
+    __syncthreads();  // the passes below read what other threads of this workgroup wrote
+    x = m;
+  }
+  vl_select4(x, n, a.rank, hist, wtot, sel);
   __syncthreads();
   if (tid < 2) {  // numpy's _lerp on (previous, next, gamma): the difference is an fp32 subtraction, the rest double
     const float lo = vl_unkey(sel[2 * tid]), hi = vl_unkey(sel[2 * tid + 1]);

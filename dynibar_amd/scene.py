@@ -17,9 +17,10 @@ integers:
 frame: the same keys, shapes, dtypes and bits.  The pixel indices come from ``sample_ray.rng`` by ``sample_random_pixel``'s own logic, so the
 reference's index stream is unchanged and shared with the host sampler.
 
-What stays host work of the caller, once per scene: reading and decoding the files, ``cv2.resize``, the disk erosion of the motion mask
-(monocular.py:177-204) and ``disp / scale``.  cv2, skimage and imageio were not available when this was written, so their semantics are not
-restated here: the arrays are taken as the caller's own loader produces them.
+What stays host work of the caller, once per scene: reading and decoding the files.  ``cv2.resize``, the disk erosion of the motion mask
+(monocular.py:177-204) and ``disp / scale`` have device forms in ``dynibar_amd.ingest`` (restated contracts, believed but not verified against
+cv2 / skimage), and ``DeviceScene.from_decoded`` runs them in front of the constructor.  The constructors take the arrays as a loader produces
+them, as host arrays or as torch tensors that are already on the scene's device; those are adopted without a round trip through the host (their 0 / 1 check brings back one boolean per store).
 
 Bullet-time frames (render_monocular_bt.py) come from the same resident scene, which then needs no training stores:
 
@@ -73,6 +74,20 @@ def _host_tensor(x):
     return torch.from_numpy(np.ascontiguousarray(x))
 
 
+def _adopt(x, what, device):
+  """a torch tensor that already lives on the scene's device is taken as it is (checked with device operations, never brought to the host);
+  anything else becomes a host array"""
+  if isinstance(x, torch.Tensor) and x.device.type == device.type == 'cuda' and x.device.index == (
+      device.index if device.index is not None else torch.cuda.current_device()):
+    return x.detach().contiguous()
+  return _np(x, what)
+
+
+def _dtype(x):
+  """'uint8', 'float32', ...: of a numpy array or of a torch tensor"""
+  return str(x.dtype).replace('torch.', '')
+
+
 def _shape(x, want, what):
   if tuple(x.shape) != tuple(want):
     raise ValueError(f'{what} must be {list(want)}, got {list(x.shape)}')
@@ -80,7 +95,14 @@ def _shape(x, want, what):
 
 
 def _binary_u8(x, want, what):
-  """a 0 / 1 mask given as uint8, bool or float32 -> uint8 0 / 1"""
+  """a 0 / 1 mask given as uint8, bool or float32 -> uint8 0 / 1 (a device tensor stays on its device)"""
+  if isinstance(x, torch.Tensor) and x.is_cuda:
+    _shape(x, want, what)
+    if _dtype(x) not in ('uint8', 'bool', 'float32'):
+      raise ValueError(f'{what} must be uint8, bool or float32, got {_dtype(x)}')
+    if x.dtype != torch.bool and not bool(torch.logical_or(x == 0, x == 1).all()):
+      raise ValueError(f'{what} must hold only 0 and 1')
+    return x.to(torch.uint8).contiguous()
   x = _shape(_np(x, what), want, what)
   if x.dtype not in (np.uint8, np.bool_, np.float32):
     raise ValueError(f'{what} must be uint8, bool or float32, got {x.dtype}')
@@ -144,12 +166,26 @@ class DeviceScene(object):
   source_masks   None, or the masks ``args.mask_src_view`` multiplies the static source views by (monocular.py:131-142): uint8 ``[N, H, W]``
                  or ``[N, H, W, 3]`` as decoded, 0..255 (the view is multiplied by ``m / 255``); bool or float32 0 / 1 are stored as 0 / 255
 
-  Decoding, ``cv2.resize``, the erosion and ``disp / scale`` are the caller's (module docstring).  Bad shapes or dtypes raise ValueError."""
+  Decoding is the caller's; ``cv2.resize``, the erosion and ``disp / scale`` are ``dynibar_amd.ingest``'s (``from_decoded``).  Every array may be a
+  host array or a torch tensor on ``device`` (adopted in place: a float32 or uint8 store may alias it).  Bad shapes or dtypes raise ValueError."""
 
   def __init__(self, device, images, intrinsics, poses, depth_range, disp, motion_mask, static_mask, flows, flow_masks, virtual_views,
                virtual_poses, source_masks=None):
     self._setup(device, images, intrinsics, poses, depth_range, (disp, motion_mask, static_mask, flows, flow_masks), virtual_views, virtual_poses,
                 source_masks)
+
+  @classmethod
+  def from_decoded(cls, device, frames, depth, dynamic_masks, static_masks, flows, flow_masks, virtual_views, virtual_poses, intrinsics, poses,
+                   depth_range, scale, erosion_radius, size=None, source_masks=None, batch=None):
+    """A training scene from what a caller has after DECODING a scene's files: ``dynibar_amd.ingest.prepare_monocular`` (the loader's resizes,
+    the erosion of the motion mask and ``disp / scale`` on the device, ``batch`` frames at a time; its docstring has the arguments) followed by
+    the constructor.  The full-resolution frames never pass through host-side resampling and no image data returns to the host; the
+    constructor's 0 / 1 check of a mask that is already on the device reads back one boolean per store (a synchronisation, once per scene)."""
+    from . import ingest
+    prepared = ingest.prepare_monocular(frames, depth, dynamic_masks, static_masks, flows, flow_masks, virtual_views, virtual_poses, intrinsics,
+                                        poses, depth_range, scale, erosion_radius, size=size, source_masks=source_masks,
+                                        batch=batch or ingest.DEFAULT_BATCH, device=device)
+    return cls(device, **prepared)
 
   @classmethod
   def for_rendering(cls, device, images, intrinsics, poses, depth_range, virtual_views, virtual_poses, source_masks=None):
@@ -177,8 +213,8 @@ class DeviceScene(object):
                   ``np.float32(cv2.imread(mv_masks...) > 1e-3)`` after the caller's nearest resize (:423-428)
     Entries of ``gt_views`` / ``gt_masks`` for frames outside ``3 .. N - 4`` are never read.
 
-    Reading and decoding the files and both ``cv2.resize`` modes stay the caller's, once per scene.  cv2, skimage and imageio were not
-    available when this was written, so their semantics are not restated here: the arrays are taken as the caller's own loader produces them."""
+    Reading and decoding the files stays the caller's.  Both ``cv2.resize`` modes have device forms (``dynibar_amd.ingest.resize_area``,
+    ``resize_nearest``): a caller can stream ``mv_images`` and the masks through them one time step at a time and pass device tensors here."""
     self = cls.__new__(cls)
     self._setup(device, images, intrinsics, poses, depth_range, None, None, None, coarse_masks, evaluation=(gt_views, gt_masks))
     return self
@@ -189,9 +225,10 @@ class DeviceScene(object):
     self.device = torch.device(device)
     self.made_by = 'for_evaluation' if evaluation is not None else 'for_rendering' if training is None else '__init__'
     self.missing_views = evaluation is not None
-    images = _np(images, 'images')
-    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
-      raise ValueError(f'images must be uint8 [N, H, W, 3], got {images.dtype} {list(images.shape)}')
+    adopt = lambda x, what: _adopt(x, what, self.device)
+    images = adopt(images, 'images')
+    if _dtype(images) != 'uint8' or images.ndim != 4 or images.shape[3] != 3:
+      raise ValueError(f'images must be uint8 [N, H, W, 3], got {_dtype(images)} {list(images.shape)}')
     N, H, W = (int(v) for v in images.shape[:3])
     if N < 7:
       raise ValueError(f'a scene needs at least 7 frames (the first and the last 3 are never targets), got {N}')
@@ -205,18 +242,18 @@ class DeviceScene(object):
     self.missing_stores = () if training is not None else _TRAINING_STORES
     if training is not None:
       disp, motion_mask, static_mask, flows, flow_masks = training
-      disp = _shape(_np(disp, 'disp'), (N, H, W), 'disp')
-      flows = _shape(_np(flows, 'flows'), (N, 6, H, W, 2), 'flows')
+      disp = _shape(adopt(disp, 'disp'), (N, H, W), 'disp')
+      flows = _shape(adopt(flows, 'flows'), (N, 6, H, W, 2), 'flows')
       for x, what in ((disp, 'disp'), (flows, 'flows')):
-        if x.dtype != np.float32:
-          raise ValueError(f'{what} must be float32, got {x.dtype}')
-      motion_mask = _binary_u8(motion_mask, (N, H, W), 'motion_mask')
-      static_mask = _binary_u8(static_mask, (N, H, W), 'static_mask')
-      flow_masks = _binary_u8(flow_masks, (N, 6, H, W), 'flow_masks')
+        if _dtype(x) != 'float32':
+          raise ValueError(f'{what} must be float32, got {_dtype(x)}')
+      motion_mask = _binary_u8(adopt(motion_mask, 'motion_mask'), (N, H, W), 'motion_mask')
+      static_mask = _binary_u8(adopt(static_mask, 'static_mask'), (N, H, W), 'static_mask')
+      flow_masks = _binary_u8(adopt(flow_masks, 'flow_masks'), (N, 6, H, W), 'flow_masks')
     if evaluation is None:
-      virtual_views = _shape(_np(virtual_views, 'virtual_views'), (N, NUM_VIRTUAL, H, W, 3), 'virtual_views')
-      if virtual_views.dtype != np.uint8:
-        raise ValueError(f'virtual_views must be uint8, got {virtual_views.dtype}')
+      virtual_views = _shape(adopt(virtual_views, 'virtual_views'), (N, NUM_VIRTUAL, H, W, 3), 'virtual_views')
+      if _dtype(virtual_views) != 'uint8':
+        raise ValueError(f'virtual_views must be uint8, got {_dtype(virtual_views)}')
       virtual_poses = _shape(_np(virtual_poses, 'virtual_poses'), (N, NUM_VIRTUAL, 4, 4), 'virtual_poses')
     self.virtual_poses_host = virtual_poses  # as given: bullet_time_plan computes its distances in the caller's dtype
     mask_channels = 1
@@ -224,27 +261,28 @@ class DeviceScene(object):
     if evaluation is not None:
       gt_views, gt_masks = evaluation
       if source_masks is not None:
-        source_masks = _np(source_masks, 'coarse_masks')
+        source_masks = adopt(source_masks, 'coarse_masks')
         if tuple(source_masks.shape) != (N, H, W):
           raise ValueError(f'coarse_masks must be [{N}, {H}, {W}] (one channel: the script builds its own all-ones mask as [H, W]), '
                            f'got {list(source_masks.shape)}')
-        if source_masks.dtype != np.uint8:
-          raise ValueError(f'coarse_masks must be uint8 (0..255 as decoded), got {source_masks.dtype}')
+        if _dtype(source_masks) != 'uint8':
+          raise ValueError(f'coarse_masks must be uint8 (0..255 as decoded), got {_dtype(source_masks)}')
       if gt_views is not None:
-        gt_views = _shape(_np(gt_views, 'gt_views'), (N, NUM_CAMERAS, H, W, 3), 'gt_views')
-        if gt_views.dtype != np.uint8:
-          raise ValueError(f'gt_views must be uint8, got {gt_views.dtype}')
+        gt_views = _shape(adopt(gt_views, 'gt_views'), (N, NUM_CAMERAS, H, W, 3), 'gt_views')
+        if _dtype(gt_views) != 'uint8':
+          raise ValueError(f'gt_views must be uint8, got {_dtype(gt_views)}')
       if gt_masks is not None:
-        gt_masks = _np(gt_masks, 'gt_masks')
+        gt_masks = adopt(gt_masks, 'gt_masks')
         if tuple(gt_masks.shape) not in ((N, NUM_CAMERAS, H, W), (N, NUM_CAMERAS, H, W, 3)):
           raise ValueError(f'gt_masks must be [{N}, {NUM_CAMERAS}, {H}, {W}] or [{N}, {NUM_CAMERAS}, {H}, {W}, 3], got {list(gt_masks.shape)}')
         gt_masks = _binary_u8(gt_masks, gt_masks.shape, 'gt_masks')
     if source_masks is not None:
-      source_masks = _np(source_masks, 'source_masks')
+      source_masks = adopt(source_masks, 'source_masks')
       if tuple(source_masks.shape) not in ((N, H, W), (N, H, W, 3)):
         raise ValueError(f'source_masks must be [{N}, {H}, {W}] or [{N}, {H}, {W}, 3], got {list(source_masks.shape)}')
-      if source_masks.dtype != np.uint8:
-        source_masks = _binary_u8(source_masks, source_masks.shape, 'source_masks') * np.uint8(255)
+      if _dtype(source_masks) != 'uint8':
+        source_masks = _binary_u8(source_masks, source_masks.shape, 'source_masks')
+        source_masks = source_masks * 255 if isinstance(source_masks, torch.Tensor) else source_masks * np.uint8(255)
       mask_channels = 3 if source_masks.ndim == 4 else 1
     if self.device.type != 'cuda' and _lib._REQUIRE_DEVICE:
       raise ValueError(f'DeviceScene needs a HIP device (cuda:N), got {self.device}: there is no CPU fallback')
@@ -259,8 +297,8 @@ class DeviceScene(object):
     self._frames, image_stride = self._padded(images.reshape(N, -1))
     self._vviews = self._padded(virtual_views.reshape(N * NUM_VIRTUAL, -1))[0] if virtual_views is not None else None
     self._src_masks, mask_stride = self._padded(source_masks.reshape(N, -1)) if source_masks is not None else (None, 0)
-    f32 = lambda x: _host_tensor(x.astype(np.float32, copy=False)).to(dev)
-    u8 = lambda x: _host_tensor(x).to(dev)
+    f32 = lambda x: x if isinstance(x, torch.Tensor) else _host_tensor(x.astype(np.float32, copy=False)).to(dev)  # (a device tensor: float32, adopted)
+    u8 = lambda x: x if isinstance(x, torch.Tensor) else _host_tensor(x).to(dev)
     self._intrinsics = f32(self.intrinsics_host.reshape(N, 16))
     self._poses = f32(self.poses_host.reshape(N, 16))
     self._vposes = f32(virtual_poses.reshape(N, NUM_VIRTUAL, 16)) if virtual_poses is not None else None
@@ -287,7 +325,7 @@ class DeviceScene(object):
     n, nbytes = rows.shape
     stride = (nbytes + 15) // 16 * 16
     store = torch.zeros((n, stride), dtype=torch.uint8, device=self.device)
-    store[:, :nbytes] = _host_tensor(rows).to(self.device)
+    store[:, :nbytes] = rows if isinstance(rows, torch.Tensor) else _host_tensor(rows).to(self.device)
     return store, stride
 
   # ---- view selection (host only) -------------------------------------------------------------------------------------------------

@@ -169,7 +169,8 @@ def render_frame_virtual_views(img, disp, K, c2w_ref, vv_c2w):
 
 
 def _resize(a, h, w, mode):
-  """[H,W] or [H,W,C] float array -> [h,w(,C)] float32 with F.interpolate (nearest / area / bilinear, align_corners=False).  Not cv2-exact."""
+  """[H,W] or [H,W,C] float array -> [h,w(,C)] float32 with F.interpolate (nearest / area / bilinear, align_corners=False).  Not cv2-exact
+  (``dynibar_amd.ingest`` has the cv2-style forms on the device: resize_area, resize_linear, resize_nearest)."""
   t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
   x = t[None, None] if t.dim() == 2 else t.permute(2, 0, 1)[None]
   kw = {'align_corners': False} if mode == 'bilinear' else {}

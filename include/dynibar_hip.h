@@ -862,6 +862,52 @@ typedef struct {
 } DynAdamParams;
 int dyn_adam_step(const DynAdamParams* p, void* stream);
 
+/* ====== scene preparation (save_monocular_cameras.py:90-113, monocular.py:125-204, eval_nvidia.py:387-428) ====================================
+ * The resizes the reference takes from cv2, the erosion it takes from skimage and np.percentile of a depth map, on B images per launch.
+ * The contracts restate OpenCV's and skimage's algorithms; whether they agree with the real libraries is BELIEVED, NOT VERIFIED.
+ * src is contiguous, [B] images of the stated layout.  dst image b starts at dst + b * dst_pitch (BYTES) and is contiguous within itself; the
+ * bytes between the end of an image and the next one (the padding of a pitched store) are never written.  Nothing is allocated.
+ * For an axis of source size s and destination size d: scale = 1.0 / ((double)d / s).
+ *   dyn_resize_area_u8     cv2.resize(INTER_AREA) shrinking uint8 [B,Hs,Ws,C], C in 1, 3, 4 -> [B,Hd,Wd,C].  Both scales integers
+ *                          (|scale - (int)scale| < DBL_EPSILON): the integer sum of the ix * iy block; (sum + 2) >> 2 for 2 x 2, else
+ *                          rintf((float)sum * (1.f / (ix * iy))), saturated; the tables are not read and may be null.  Otherwise the
+ *                          decimation tables of both axes (DEVICE; built by the caller in double and rounded to fp32; destination index i
+ *                          has count[i] <= K entries (idx[i][k], w[i][k])): for destination index i, f1 = i * scale, f2 = f1 + scale,
+ *                          cell = min(scale, s - f1), s1 = ceil(f1), s2 = min(floor(f2), s - 1), s1 = min(s1, s2); entries in this order:
+ *                          (s1 - 1, (s1 - f1) / cell) if s1 - f1 > 1e-3; (k, 1 / cell) for k in [s1, s2); (s2, min(min(f2 - s2, 1), cell)
+ *                          / cell) if f2 - s2 > 1e-3.  fp32, one rounded operation at a time: per source row a destination pixel starts
+ *                          at 0.f and adds (float)S[k] * alpha over the x entries in order; the destination row is the sequential sum
+ *                          of beta * rowvalue over the y entries, the first term initialising it; rintf (ties to even), saturated.
+ *                          Table indices are clamped to the source, counts to K.
+ *   dyn_resize_linear_f32  cv2.resize(INTER_LINEAR) on fp32 [B,Hs,Ws] -> [B,Hd,Wd].  Per destination index i: f = (float)((i + 0.5) *
+ *                          scale - 0.5) with the inner arithmetic in double, s0 = floor(f), f = f - (float)s0 in fp32.  Horizontally:
+ *                          s0 < 0 -> s0 = 0, f = 0; s0 >= Ws - 1 -> the value is S[Ws - 1], no second tap; else S[s0] * (1.f - f) +
+ *                          S[s0 + 1] * f.  Vertically rows s0, s0 + 1 clamped to [0, Hs - 1], weights (1.f - f) and f NOT zeroed at the
+ *                          edges: r0 * (1.f - f) + r1 * f.  Horizontal first, every product and sum rounded on its own.  reciprocal: a
+ *                          tap is 1.f / S (the disparity of a depth map); divide: the result is divided by divisor (non-zero) in fp32.
+ *   dyn_resize_nearest     cv2.resize(INTER_NEAREST) on pixels of 1, 3, 4, 8 or 12 bytes: source index min((int)floor(i * scale), s - 1)
+ *                          per axis, in double.  below >= 0: the destination is uint8 [B,Hd,Wd], (first byte of the pixel < below) ? 1 : 0
+ *                          (below = 255 is the loader's 1 - m / 255 > 1e-3 on a decoded uint8 m); below = -1: the pixel is copied.
+ *   dyn_erode_disk_u8      skimage.morphology.erosion(mask, disk(radius)) on 0 / 1 uint8 [B,H,W], radius 0..15: out = AND over the IN-IMAGE
+ *                          (y + dy, x + dx) with dx*dx + dy*dy <= radius*radius of (src != 0); src and dst must not overlap.
+ *   dyn_percentile_pair    two percentiles by numpy's `linear` method for each of B fp32 images of n values, image b at x + b * stride
+ *                          (elements).  rank[4] (HOST): the order statistics below and above each percentile; weight[2] (HOST): the
+ *                          interpolation weights; as dyn_viewlog_ranges selects them.  single: fp32 arithmetic throughout, out fp32
+ *                          [B][2] (np.percentile(x, q) with a scalar q); else a + fp32(b - a) t in double, out double [B][2].  DEVICE out.
+ * Refused before a launch, DYN_E_INVALID: null or misaligned pointers, sizes below 1, an image of 2^31 bytes or more, B or Hd above 65535,
+ * a dst_pitch smaller than an image, an enlarging INTER_AREA, a missing table, C / pixel_bytes / radius / below / rank / weight outside
+ * their ranges. */
+int dyn_resize_area_u8(int B, int Hs, int Ws, int C, int Hd, int Wd, const void* src, void* dst, int64_t dst_pitch, const int32_t* xcount,
+                       const int32_t* xidx, const float* xw, int Kx, const int32_t* ycount, const int32_t* yidx, const float* yw, int Ky,
+                       void* stream);
+int dyn_resize_linear_f32(int B, int Hs, int Ws, int Hd, int Wd, const float* src, float* dst, int64_t dst_pitch, int reciprocal, int divide,
+                          float divisor, void* stream);
+int dyn_resize_nearest(int B, int Hs, int Ws, int pixel_bytes, int Hd, int Wd, const void* src, void* dst, int64_t dst_pitch, int below,
+                       void* stream);
+int dyn_erode_disk_u8(int B, int H, int W, int radius, const void* src, void* dst, int64_t dst_pitch, void* stream);
+int dyn_percentile_pair(int B, int64_t n, const float* x, int64_t stride, const int32_t* rank, const double* weight, int single, void* out,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
