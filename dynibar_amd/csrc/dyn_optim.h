@@ -14,6 +14,17 @@
 //                 The workgroup reads its tensor's record through wave-uniform loads; the data pointers come from that record, so the
 //                 accesses are flat_load / flat_store_dwordx4.  A chunk takes the float4 path when p, g, m and v are
 //                 all 16-byte aligned at its first element (4096 elements keep the alignment of the tensor's start), else single floats.
+//
+// The guard of the step (include/dynibar_hip.h states the contract): the global gradient norm, clipping by it and skipping a step whose
+// gradients are not finite, as three plain launches in stream order -- no tickets, no atomics, nothing for the host to read.
+//   k_grad_sumsq         the grid of k_adam_step.  One more streaming read of the gradients (4 bytes per element): a full aligned chunk is
+//                        four float4 loads per thread, all issued before the first addition.  Element e belongs to lane (e >> 2) & 255
+//                        on every path, so the double sum of a chunk does not depend on the alignment of g.  Every chunk stores its
+//                        partial, a skipped one 0.0: the buffer never needs clearing.
+//   k_grad_stats         one workgroup adds the partials (a few hundred doubles) and writes sumsq, norm, coef, finite and the two counters.
+//   k_adam_step_guarded  the body of k_adam_step (one template; the unguarded instantiation is the kernel as it was) with g * coef in front
+//                        of the update and a wave-uniform way out for a held step; coef and finite come through scalar loads.
+//   k_grad_scale         the stand-alone clip: g = g * coef in place, nothing written when coef == 1.
 #pragma once
 
 #define ADAM_THREADS 256
@@ -38,9 +49,22 @@ __device__ __forceinline__ void adam_update4(float4& p, const float4& g, float4&
   adam_update(p.w, g.w, m.w, v.w, k);
 }
 
-// grid n_chunks, block ADAM_THREADS
-__global__ __launch_bounds__(ADAM_THREADS) void k_adam_step(const DynAdamTensor* __restrict__ tensors, int n_tensors, const int2* __restrict__ chunks,
-                                                            int n_chunks, int zero_grads) {
+// the gradient the update sees: g itself, or g * coef under the guard (one fp32 multiplication)
+template <bool GUARDED>
+__device__ __forceinline__ float adam_grad(const float g, const float coef) {
+  if constexpr (GUARDED) return g * coef;
+  return g;
+}
+template <bool GUARDED>
+__device__ __forceinline__ float4 adam_grad4(const float4& g, const float coef) {
+  if constexpr (GUARDED) return make_float4(g.x * coef, g.y * coef, g.z * coef, g.w * coef);
+  return g;
+}
+
+// One chunk of the step.  GUARDED = false is k_adam_step as it always was: stats is not read and every use of coef folds away.
+template <bool GUARDED>
+__device__ __forceinline__ void adam_step_chunk(const DynAdamTensor* __restrict__ tensors, int n_tensors, const int2* __restrict__ chunks,
+                                                int n_chunks, int zero_grads, const DynGradStats* __restrict__ stats, int skip_nonfinite) {
   const int c = blockIdx.x, tid = threadIdx.x;
   if (c >= n_chunks) return;
   const int2 ch = chunks[c];
@@ -54,13 +78,22 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_adam_step(const DynAdamTensor*
   float* g = t.g + start;
   float* m = t.m + start;
   float* v = t.v + start;
+  float coef = 1.f;
+  if constexpr (GUARDED) {
+    coef = stats->coef;
+    if (skip_nonfinite && stats->finite == 0) {  // a held step: p, m and v stay as they are
+      if (zero_grads)
+        for (int e = tid; e < len; e += ADAM_THREADS) g[e] = 0.f;
+      return;
+    }
+  }
   AdamScalars k;
   k.a = t.a; k.s2 = t.s2; k.c1 = t.c1; k.c2 = t.c2; k.beta2 = t.beta2; k.eps = t.eps;
   const uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
   if ((bits & 15) != 0) {
     for (int e = tid; e < len; e += ADAM_THREADS) {
       float pe = p[e], me = m[e], ve = v[e];
-      const float ge = g[e];
+      const float ge = adam_grad<GUARDED>(g[e], coef);
       adam_update(pe, ge, me, ve, k);
       p[e] = pe; m[e] = me; v[e] = ve;
       if (zero_grads) g[e] = 0.f;
@@ -82,7 +115,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_adam_step(const DynAdamTensor*
 #pragma unroll
     for (int r = 0; r < ADAM_ROUNDS; ++r) {
       const int i = r * ADAM_THREADS + tid;
-      adam_update4(pp[r], gg[r], mm[r], vv[r], k);
+      adam_update4(pp[r], adam_grad4<GUARDED>(gg[r], coef), mm[r], vv[r], k);
       p4[i] = pp[r]; m4[i] = mm[r]; v4[i] = vv[r];
       if (zero_grads) g4[i] = zero;
     }
@@ -91,31 +124,203 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_adam_step(const DynAdamTensor*
   const int n4 = len >> 2;
   for (int i = tid; i < n4; i += ADAM_THREADS) {
     float4 pe = p4[i], me = m4[i], ve = v4[i];
-    const float4 ge = g4[i];
+    const float4 ge = adam_grad4<GUARDED>(g4[i], coef);
     adam_update4(pe, ge, me, ve, k);
     p4[i] = pe; m4[i] = me; v4[i] = ve;
     if (zero_grads) g4[i] = zero;
   }
   for (int e = 4 * n4 + tid; e < len; e += ADAM_THREADS) {  // the last 1..3 elements of the tensor
     float pe = p[e], me = m[e], ve = v[e];
-    const float ge = g[e];
+    const float ge = adam_grad<GUARDED>(g[e], coef);
     adam_update(pe, ge, me, ve, k);
     p[e] = pe; m[e] = me; v[e] = ve;
     if (zero_grads) g[e] = 0.f;
   }
 }
 
+// grid n_chunks, block ADAM_THREADS
+__global__ __launch_bounds__(ADAM_THREADS) void k_adam_step(const DynAdamTensor* __restrict__ tensors, int n_tensors, const int2* __restrict__ chunks,
+                                                            int n_chunks, int zero_grads) {
+  adam_step_chunk<false>(tensors, n_tensors, chunks, n_chunks, zero_grads, nullptr, 0);
+}
+
+// grid n_chunks, block ADAM_THREADS
+__global__ __launch_bounds__(ADAM_THREADS) void k_adam_step_guarded(const DynAdamTensor* __restrict__ tensors, int n_tensors,
+                                                                    const int2* __restrict__ chunks, int n_chunks, int zero_grads,
+                                                                    const DynGradStats* __restrict__ stats, int skip_nonfinite) {
+  adam_step_chunk<true>(tensors, n_tensors, chunks, n_chunks, zero_grads, stats, skip_nonfinite);
+}
+
+// The 256 lane sums of a workgroup -> one double, the same in every thread: the xor butterfly within each wave (met_wave_sum), then
+// ((w0 + w1) + w2) + w3.  Every thread of the workgroup must call it.
+__device__ __forceinline__ double grad_block_sum(double v, double* red) {
+  v = met_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__device__ __forceinline__ void grad_add(double& s, const float g) { s += (double)g * (double)g; }
+
+#define GRAD_LDS (sizeof(double) * (ADAM_THREADS / 64))
+
+// grid n_chunks, block ADAM_THREADS, LDS GRAD_LDS
+__global__ __launch_bounds__(ADAM_THREADS) void k_grad_sumsq(const DynAdamTensor* __restrict__ tensors, int n_tensors, const int2* __restrict__ chunks,
+                                                             int n_chunks, double* __restrict__ partials) {
+  double* red = reinterpret_cast<double*>(dyn_smem);  // [ADAM_THREADS / 64] wave sums
+  const int c = blockIdx.x, tid = threadIdx.x;
+  if (c >= n_chunks) return;
+  const int2 ch = chunks[c];
+  int len = 0;  // stays 0 for a chunk that is skipped or lies outside the records: it stores 0.0
+  const float* g = nullptr;
+  if (ch.x >= 0 && ch.x < n_tensors && ch.y >= 0) {
+    const DynAdamTensor t = tensors[ch.x];
+    const long start = (long)ch.y * DYN_ADAM_CHUNK;
+    if (!t.skip && start < t.n) {
+      const long left = t.n - start;
+      len = left < DYN_ADAM_CHUNK ? (int)left : DYN_ADAM_CHUNK;
+      g = t.g + start;
+    }
+  }
+  double s = 0.0;
+  if (len > 0) {
+    const int n4 = len >> 2;  // whole groups of four elements; group i belongs to lane i & 255
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+      const float4* g4 = reinterpret_cast<const float4*>(g);
+      if (len == DYN_ADAM_CHUNK) {  // a full chunk: all four loads before the first addition
+        float4 gg[ADAM_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < ADAM_ROUNDS; ++r) gg[r] = g4[r * ADAM_THREADS + tid];
+#pragma unroll
+        for (int r = 0; r < ADAM_ROUNDS; ++r) {
+          grad_add(s, gg[r].x); grad_add(s, gg[r].y); grad_add(s, gg[r].z); grad_add(s, gg[r].w);
+        }
+      } else {
+        for (int i = tid; i < n4; i += ADAM_THREADS) {
+          const float4 ge = g4[i];
+          grad_add(s, ge.x); grad_add(s, ge.y); grad_add(s, ge.z); grad_add(s, ge.w);
+        }
+      }
+    } else {
+      for (int i = tid; i < n4; i += ADAM_THREADS) {
+        const float* ge = g + 4 * i;
+        grad_add(s, ge[0]); grad_add(s, ge[1]); grad_add(s, ge[2]); grad_add(s, ge[3]);
+      }
+    }
+    if (tid == (n4 & (ADAM_THREADS - 1)))  // the last 1..3 elements of the tensor are group n4: after every earlier group of its lane
+      for (int e = 4 * n4; e < len; ++e) grad_add(s, g[e]);
+  }
+  s = grad_block_sum(s, red);
+  if (tid == 0) partials[c] = s;
+}
+
+// grid 1, block ADAM_THREADS, LDS GRAD_LDS
+__global__ __launch_bounds__(ADAM_THREADS) void k_grad_stats(const double* __restrict__ partials, int n_chunks, DynGradStats* __restrict__ stats,
+                                                             float max_norm, int count) {
+  double* red = reinterpret_cast<double*>(dyn_smem);  // [ADAM_THREADS / 64] wave sums
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int i = tid; i < n_chunks; i += ADAM_THREADS) s += partials[i];
+  s = grad_block_sum(s, red);
+  if (tid != 0) return;
+  const int finite = __builtin_isfinite(s) ? 1 : 0;
+  const float norm = (float)sqrt(s);
+  float coef = 1.0f;
+  if (max_norm > 0.f && finite) coef = fminf(1.0f, max_norm / (norm + 1e-6f));
+  stats->sumsq = s;
+  stats->norm = norm;
+  stats->coef = coef;
+  stats->finite = finite;
+  stats->reserved = 0;
+  if (count) {
+    stats->calls = stats->calls + 1;
+    if (!finite) stats->nonfinite = stats->nonfinite + 1;
+  }
+}
+
+// grid n_chunks, block ADAM_THREADS
+__global__ __launch_bounds__(ADAM_THREADS) void k_grad_scale(const DynAdamTensor* __restrict__ tensors, int n_tensors, const int2* __restrict__ chunks,
+                                                             int n_chunks, const DynGradStats* __restrict__ stats) {
+  const int c = blockIdx.x, tid = threadIdx.x;
+  if (c >= n_chunks) return;
+  const float coef = stats->coef;
+  if (coef == 1.0f) return;  // g * 1 is g: nothing to write
+  const int2 ch = chunks[c];
+  if (ch.x < 0 || ch.x >= n_tensors || ch.y < 0) return;
+  const DynAdamTensor t = tensors[ch.x];
+  const long start = (long)ch.y * DYN_ADAM_CHUNK;
+  if (t.skip || start >= t.n) return;
+  const long left = t.n - start;
+  const int len = left < DYN_ADAM_CHUNK ? (int)left : DYN_ADAM_CHUNK;
+  float* g = t.g + start;
+  if ((reinterpret_cast<uintptr_t>(g) & 15) != 0) {
+    for (int e = tid; e < len; e += ADAM_THREADS) g[e] = g[e] * coef;
+    return;
+  }
+  float4* g4 = reinterpret_cast<float4*>(g);
+  const int n4 = len >> 2;
+  for (int i = tid; i < n4; i += ADAM_THREADS) {
+    const float4 ge = g4[i];
+    g4[i] = make_float4(ge.x * coef, ge.y * coef, ge.z * coef, ge.w * coef);
+  }
+  for (int e = 4 * n4 + tid; e < len; e += ADAM_THREADS) g[e] = g[e] * coef;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------
+// what every entry point here refuses about the records and the chunk list
+static int adam_tables_ok(const char* who, const void* tensors, int n_tensors, const void* chunks, int n_chunks) {
+  DYN_REQUIRE(tensors && chunks, "%s: tensors and chunks are required", who);
+  DYN_REQUIRE(n_tensors >= 1 && n_chunks >= 1, "%s: %d tensors in %d chunks (both >= 1)", who, n_tensors, n_chunks);
+  DYN_REQUIRE((reinterpret_cast<uintptr_t>(tensors) & 7) == 0 && (reinterpret_cast<uintptr_t>(chunks) & 7) == 0,
+              "%s: tensors and chunks must start on 8 bytes", who);
+  return 0;
+}
+
 extern "C" int dyn_adam_step(const DynAdamParams* p, void* stream) {
   const char* who = "dyn_adam_step";
   DYN_REQUIRE(p, "%s: null params", who);
-  DYN_REQUIRE(p->tensors && p->chunks, "%s: tensors and chunks are required", who);
-  DYN_REQUIRE(p->n_tensors >= 1 && p->n_chunks >= 1, "%s: %d tensors in %d chunks (both >= 1)", who, p->n_tensors, p->n_chunks);
-  DYN_REQUIRE((reinterpret_cast<uintptr_t>(p->tensors) & 7) == 0 && (reinterpret_cast<uintptr_t>(p->chunks) & 7) == 0,
-              "%s: tensors and chunks must start on 8 bytes", who);
+  if (const int rc = adam_tables_ok(who, p->tensors, p->n_tensors, p->chunks, p->n_chunks)) return rc;
   DYN_LAUNCH(DYN_K_ADAM_STEP, who, k_adam_step, dim3((unsigned)p->n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream,
              static_cast<const DynAdamTensor*>(p->tensors), p->n_tensors, reinterpret_cast<const int2*>(p->chunks), p->n_chunks, p->zero_grads ? 1 : 0);
+  return 0;
+}
+
+extern "C" int dyn_grad_norm(const DynGradNormParams* p, void* stream) {
+  const char* who = "dyn_grad_norm";
+  DYN_REQUIRE(p, "%s: null params", who);
+  if (const int rc = adam_tables_ok(who, p->tensors, p->n_tensors, p->chunks, p->n_chunks)) return rc;
+  DYN_REQUIRE(p->partials && p->stats, "%s: partials and stats are required", who);
+  DYN_REQUIRE((reinterpret_cast<uintptr_t>(p->partials) & 7) == 0 && (reinterpret_cast<uintptr_t>(p->stats) & 7) == 0,
+              "%s: partials and stats must start on 8 bytes", who);
+  DYN_REQUIRE(p->max_norm == p->max_norm, "%s: max_norm is NaN", who);
+  DYN_LAUNCH(DYN_K_GRAD_SUMSQ, who, k_grad_sumsq, dim3((unsigned)p->n_chunks), dim3(ADAM_THREADS), GRAD_LDS, (hipStream_t)stream,
+             static_cast<const DynAdamTensor*>(p->tensors), p->n_tensors, reinterpret_cast<const int2*>(p->chunks), p->n_chunks, p->partials);
+  DYN_LAUNCH(DYN_K_GRAD_STATS, who, k_grad_stats, dim3(1), dim3(ADAM_THREADS), GRAD_LDS, (hipStream_t)stream,
+             static_cast<const double*>(p->partials), p->n_chunks, p->stats, p->max_norm, p->count ? 1 : 0);
+  return 0;
+}
+
+extern "C" int dyn_grad_scale(const DynGradScaleParams* p, void* stream) {
+  const char* who = "dyn_grad_scale";
+  DYN_REQUIRE(p, "%s: null params", who);
+  if (const int rc = adam_tables_ok(who, p->tensors, p->n_tensors, p->chunks, p->n_chunks)) return rc;
+  DYN_REQUIRE(p->stats, "%s: stats is required", who);
+  DYN_REQUIRE((reinterpret_cast<uintptr_t>(p->stats) & 7) == 0, "%s: stats must start on 8 bytes", who);
+  DYN_LAUNCH(DYN_K_GRAD_SCALE, who, k_grad_scale, dim3((unsigned)p->n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream,
+             static_cast<const DynAdamTensor*>(p->tensors), p->n_tensors, reinterpret_cast<const int2*>(p->chunks), p->n_chunks, p->stats);
+  return 0;
+}
+
+extern "C" int dyn_adam_step_guarded(const DynAdamGuardedParams* p, void* stream) {
+  const char* who = "dyn_adam_step_guarded";
+  DYN_REQUIRE(p, "%s: null params", who);
+  if (const int rc = adam_tables_ok(who, p->tensors, p->n_tensors, p->chunks, p->n_chunks)) return rc;
+  DYN_REQUIRE(p->stats, "%s: stats is required", who);
+  DYN_REQUIRE((reinterpret_cast<uintptr_t>(p->stats) & 7) == 0, "%s: stats must start on 8 bytes", who);
+  DYN_LAUNCH(DYN_K_ADAM_STEP_GUARDED, who, k_adam_step_guarded, dim3((unsigned)p->n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream,
+             static_cast<const DynAdamTensor*>(p->tensors), p->n_tensors, reinterpret_cast<const int2*>(p->chunks), p->n_chunks,
+             p->zero_grads ? 1 : 0, p->stats, p->skip_nonfinite ? 1 : 0);
   return 0;
 }

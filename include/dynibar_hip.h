@@ -862,6 +862,73 @@ typedef struct {
 } DynAdamParams;
 int dyn_adam_step(const DynAdamParams* p, void* stream);
 
+/* ------ the guard of the step: the global gradient norm, clipping by it, skipping a step whose gradients are not finite -----------------
+ * Three plain launches in stream order over the records and the chunk list of dyn_adam_step: k_grad_sumsq (one workgroup per chunk) and
+ * k_grad_stats (one workgroup) by dyn_grad_norm, then k_adam_step_guarded (or k_grad_scale for a stand-alone clip).  No atomics, no
+ * counters between workgroups, nothing read back by the host.  The norm reads only g, n and skip of a record.  Every bit is decided here:
+ *   chunk sum    One workgroup of 256 threads per chunk.  Element e of a chunk (0 <= e < len <= DYN_ADAM_CHUNK) belongs to lane
+ *                (e >> 2) & 255 -- the float4 assignment of k_adam_step -- whatever the alignment of g: a chunk read in single floats sums
+ *                the same elements per lane in the same order as one read in float4s.  A lane starts from 0.0 and adds
+ *                (double)g[e] * (double)g[e] for its elements in increasing e; the product of two fp32 values is exact in double
+ *                (subnormals included), each addition is rounded once.  The 256 lane sums are reduced within each wave of 64 by
+ *                v += shfl_xor(v, m) for m = 32, 16, 8, 4, 2, 1, and the four wave sums are added as ((w0 + w1) + w2) + w3.  The result
+ *                goes to partials[c]; a chunk whose record has skip != 0, or whose tensor index or first element lies outside the
+ *                records, stores 0.0.  Every entry of partials is written by every call: it never needs clearing.
+ *   finish       One workgroup of 256 threads.  Lane l adds partials[l], partials[l + 256], ... in that order from 0.0; the same
+ *                reduction gives sumsq.  finite = isfinite(sumsq): the squares cannot overflow double, so finite is 0 exactly when some
+ *                gradient element is Inf or NaN.  norm = (float)sqrt(sumsq), the correctly rounded double square root rounded to fp32
+ *                once; norm can be +Inf while finite == 1 (two elements of 3e38: sumsq = 1.8e77).  coef in fp32, every operation rounded
+ *                once: 1.0f when max_norm <= 0 or finite == 0, otherwise fminf(1.0f, max_norm / (norm + 1e-6f)) -- torch's
+ *                clip_grad_norm_ with one correctly rounded division.  An infinite norm under clipping therefore gives coef = 0: the
+ *                guarded step then moves the parameters by the moments alone.  With count != 0 one thread does calls += 1 and, when
+ *                finite == 0, nonfinite += 1, by plain loads and stores (one workgroup; calls are ordered by the stream).
+ *   guarded step The grid, the paths and the data movement of k_adam_step.  Every workgroup reads stats->coef and stats->finite.  If
+ *                skip_nonfinite != 0 and finite == 0: p, m and v are not written; with zero_grads the gradients are still cleared.
+ *                Otherwise g' = g * coef (one fp32 multiplication; coef == 1 is the identity), then the update of dyn_adam_step on g'.
+ *                g itself is never rewritten with g': the step stores no gradients other than the zeros of zero_grads.
+ *   scale        g = g * stats->coef in place for every record with skip == 0 (one fp32 multiplication per element); with coef == 1
+ *                nothing is written.
+ * Refused before a launch, DYN_E_INVALID: null params, records, chunks, partials or stats (each where the call takes it), counts below 1,
+ * records, chunks, partials or stats not on 8 bytes, a NaN max_norm. */
+typedef struct {
+  double  sumsq;               /* sum of g*g over every element of every record with skip == 0 */
+  float   norm;                /* (float)sqrt(sumsq): double sqrt, then one rounding to fp32 */
+  float   coef;                /* the clip factor */
+  int32_t finite;              /* 1 when sumsq is finite, i.e. when every gradient element is */
+  int32_t reserved;
+  int64_t calls;               /* += 1 per dyn_grad_norm call with count != 0 */
+  int64_t nonfinite;           /* += 1 per such call with finite == 0 */
+} DynGradStats;                /* DEVICE, 8-byte aligned; the caller zeroes it once */
+typedef struct {
+  const void* tensors;         /* DEVICE [n_tensors] DynAdamTensor, 8-byte aligned: g, n and skip are read */
+  int n_tensors;
+  const int32_t* chunks;       /* DEVICE [n_chunks][2], as for dyn_adam_step */
+  int n_chunks;
+  double* partials;            /* DEVICE [n_chunks], written in full */
+  DynGradStats* stats;         /* DEVICE */
+  float max_norm;              /* <= 0: no clipping (coef = 1) */
+  int count;                   /* != 0: calls and nonfinite advance */
+} DynGradNormParams;
+int dyn_grad_norm(const DynGradNormParams* p, void* stream);
+typedef struct {
+  const void* tensors;
+  int n_tensors;
+  const int32_t* chunks;
+  int n_chunks;
+  const DynGradStats* stats;   /* DEVICE: coef is read */
+} DynGradScaleParams;
+int dyn_grad_scale(const DynGradScaleParams* p, void* stream);
+typedef struct {
+  const void* tensors;         /* the fields of DynAdamParams ... */
+  int n_tensors;
+  const int32_t* chunks;
+  int n_chunks;
+  int zero_grads;
+  int skip_nonfinite;          /* 0 / 1 */
+  const DynGradStats* stats;   /* DEVICE: coef and finite are read (dyn_grad_norm on the same stream before this call) */
+} DynAdamGuardedParams;
+int dyn_adam_step_guarded(const DynAdamGuardedParams* p, void* stream);
+
 /* ====== scene preparation (save_monocular_cameras.py:90-113, monocular.py:125-204, eval_nvidia.py:387-428) ====================================
  * The resizes the reference takes from cv2, the erosion it takes from skimage and np.percentile of a depth map, on B images per launch.
  * The contracts restate OpenCV's and skimage's algorithms; whether they agree with the real libraries is BELIEVED, NOT VERIFIED.

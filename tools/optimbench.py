@@ -11,7 +11,12 @@ parameters: (1) this optimizer, (2) torch.optim.Adam with its default implementa
 legs --, (4) torch.optim.Adam(foreach=False), the per-tensor loop the reference's torch ran.  A leg is `inner` steps timed by the host clock
 around work that ends in a stream synchronise.  In a separate pass the kernel's own time comes from the library's events, and with it the
 bytes the kernel moves (16 read and 12 written per element) over that time.  The loop leaves the ~30 MB working set in the 256 MiB Infinity
-Cache between steps; in training the rest of the iteration passes through the cache in between.  No ratio is fixed in advance."""
+Cache between steps; in training the rest of the iteration passes through the cache in between.  No ratio is fixed in advance.
+The guard (step(max_grad_norm=..., skip_nonfinite=True): k_grad_sumsq, k_grad_stats, k_adam_step_guarded) is timed in a pass of its own after those,
+so the four legs above keep their layout: the guarded step twice (the spread of two identical legs), torch.nn.utils.clip_grad_norm_ followed by
+torch.optim.Adam.step() on the same gradients, and optim.grad_norm alone.  The legs share their gradient tensors, so max_norm is far above the norm:
+coef is 1, torch multiplies every gradient by 1.0 (its cost is the same, the gradients stay), the guarded kernel multiplies by 1 as it always does.
+One guarded step is first compared with the restatement of tests/optim_guard_cases.py, exactly; the three kernels' own times come from the events."""
 import argparse
 import json
 import os
@@ -102,6 +107,47 @@ def run(rounds, inner, dev='cuda:0'):
       torch.cuda.synchronize()
       if r >= 2:
         clear[name].append((time.perf_counter() - t0) * 1e3 / inner)
+  # the guard, in a pass of its own
+  import optim_guard_cases as gc
+  ps, opt = make(optim.Adam)
+  flat = [g.reshape(-1) for gs in host_grads for g in gs]
+  partials, st = gc.restate_norm(flat, optim.CHUNK, 1.0)
+  opt.step(max_grad_norm=1.0, skip_nonfinite=True)
+  torch.cuda.synchronize()
+  gc.same64(partials, opt._tables['partials'], 'partials')
+  oc.same(np.array([st['norm']]), opt.grad_stats.norm, 'norm')
+  oc.same(np.array([st['coef']]), opt.grad_stats.coef, 'coef')
+  assert st['coef'] < 1 and int(opt.grad_stats.finite) == 1
+  for (lr, arrs), pg, gs in zip(groups, ps, host_grads):
+    for a, p, g in zip(arrs, pg, gs):
+      n = a.size
+      wp, wm, wv = oc.restate(a.reshape(-1), gc.scaled(g.reshape(-1), st['coef']), np.zeros(n, np.float32), np.zeros(n, np.float32), lr, 0.9, 0.999,
+                              1e-8, 1)
+      oc.same(wp, p, 'guarded p')
+      oc.same(wm, opt.state[p]['exp_avg'], 'guarded m')
+      oc.same(wv, opt.state[p]['exp_avg_sq'], 'guarded v')
+  FAR = 1e30
+  tps, topt = make(torch.optim.Adam)
+  tflat = [p for pg in tps for p in pg]
+
+  def torch_clip_step():
+    torch.nn.utils.clip_grad_norm_(tflat, FAR)
+    topt.step()
+
+  guarded = [make(optim.Adam)[1] for _ in range(2)]
+  guard_legs = [('hip_guarded', lambda: guarded[0].step(max_grad_norm=FAR, skip_nonfinite=True)), ('torch_clip_then_step', torch_clip_step),
+                ('hip_guarded_again', lambda: guarded[1].step(max_grad_norm=FAR, skip_nonfinite=True)),
+                ('hip_unguarded', legs[0][1].step), ('hip_grad_norm_alone', lambda: optim.grad_norm(tflat))]
+  gtimes = {name: [] for name, _ in guard_legs}
+  for r in range(rounds + 2):
+    for name, fn in guard_legs:
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      for _ in range(inner):
+        fn()
+      torch.cuda.synchronize()
+      if r >= 2:
+        gtimes[name].append((time.perf_counter() - t0) * 1e3 / inner)
   # the kernel's own time
   lib = _lib.lib()
   nk = lib.dyn_profile_count()
@@ -117,6 +163,15 @@ def run(rounds, inner, dev='cuda:0'):
   kern = {lib.dyn_profile_name(i).decode(): (float(ms[i]) / int(cnt[i]), int(cnt[i])) for i in range(nk) if cnt[i]}
   assert list(kern) == ['k_adam_step'] and kern['k_adam_step'][1] == rounds * inner, kern
   kernel_ms = kern['k_adam_step'][0]
+  lib.dyn_profile_enable(1)
+  lib.dyn_profile_read(ms.ctypes.data, cnt.ctypes.data)
+  for _ in range(rounds * inner):
+    guarded[0].step(max_grad_norm=FAR, skip_nonfinite=True)
+  torch.cuda.synchronize()
+  lib.dyn_profile_read(ms.ctypes.data, cnt.ctypes.data)
+  lib.dyn_profile_enable(0)
+  gkern = {lib.dyn_profile_name(i).decode(): (float(ms[i]) / int(cnt[i]), int(cnt[i])) for i in range(nk) if cnt[i]}
+  assert sorted(gkern) == ['k_adam_step_guarded', 'k_grad_stats', 'k_grad_sumsq'] and all(c == rounds * inner for _, c in gkern.values()), gkern
   elements = sum(a.size for _, arrs in groups for a in arrs)
   tensors = sum(len(arrs) for _, arrs in groups)
   moved = 28 * elements
@@ -124,12 +179,19 @@ def run(rounds, inner, dev='cuda:0'):
   res = {name: q(v) for name, v in times.items()}
   med = {name: statistics.median(v) for name, v in times.items()}
   spread = abs(med['torch_default'] - med['torch_default_again'])
+  gmed = {name: statistics.median(v) for name, v in gtimes.items()}
+  guard = dict(step_ms={name: q(v) for name, v in gtimes.items()}, max_norm=FAR,
+               guarded_spread_ms=round(abs(gmed['hip_guarded'] - gmed['hip_guarded_again']), 4),
+               guarded_minus_unguarded_ms=round(min(gmed['hip_guarded'], gmed['hip_guarded_again']) - gmed['hip_unguarded'], 4),
+               guarded_minus_torch_clip_then_step_ms=round(min(gmed['hip_guarded'], gmed['hip_guarded_again']) - gmed['torch_clip_then_step'], 4),
+               kernel_ms={k: round(v[0], 5) for k, v in sorted(gkern.items())}, kernels_ms=round(sum(v[0] for v in gkern.values()), 5),
+               sumsq_tb_per_s=round(4 * elements / (gkern['k_grad_sumsq'][0] * 1e-3) / 1e12, 3))
   return dict(tensors=tensors, elements=elements, groups=len(groups), chunks=hip._tables['n_chunks'], chunk=optim.CHUNK, rounds=rounds, inner=inner,
               step_ms=res, clearing_ms={k: q(v) for k, v in clear.items()}, torch_default_spread_ms=round(spread, 4),
               hip_minus_torch_default_ms=round(med['hip'] - min(med['torch_default'], med['torch_default_again']), 4),
               hip_no_slower_than_torch_default=bool(med['hip'] <= max(med['torch_default'], med['torch_default_again']) + spread),
               kernel_ms=round(kernel_ms, 5), kernel_bytes=moved, kernel_tb_per_s=round(moved / (kernel_ms * 1e-3) / 1e12, 3),
-              share_of_8_tb_per_s=round(moved / (kernel_ms * 1e-3) / 8e12, 3), exact=True, device=torch.cuda.get_device_name(0), torch=torch.__version__)
+              share_of_8_tb_per_s=round(moved / (kernel_ms * 1e-3) / 8e12, 3), exact=True, guard=guard, device=torch.cuda.get_device_name(0), torch=torch.__version__)
 
 
 def main():

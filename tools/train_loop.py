@@ -2,7 +2,10 @@
 seeded scene and targets, the reference's optimizer setup (Adam over the three MLPs' parameters + the trajectory basis, model.py:339-378),
 `render_rays_mono` under grad mode, the script's loss, `loss.backward()` through the HIP training kernels, `optimizer.step()`.
 Prints the loss every few iterations; the losses must go down.     python tools/train_loop.py [iterations] [rays] [--encoders] [--optimizer hip|torch]
+                                                                                              [--max-grad-norm X] [--skip-nonfinite]
 --optimizer hip steps with dynibar_amd.optim.Adam (one HIP launch per step) instead of torch.optim.Adam, the default.
+--max-grad-norm / --skip-nonfinite (with --optimizer hip): the guarded step -- the global gradient norm, clipping by it, no update from gradients
+that are not finite -- in three launches; the norm is printed with the loss and the counters are returned as 'grad_stats'.
 """
 import json
 import os
@@ -35,11 +38,15 @@ def main_loss(ret, batch):
   return loss + 0.05 * torch.mean(torch.abs(anc['sf_seq']))
 
 
-def run(dev='cuda:0', iters=40, R=1024, S=64, log_every=10, quiet=False, encoders=False, optimizer='torch'):
+def run(dev='cuda:0', iters=40, R=1024, S=64, log_every=10, quiet=False, encoders=False, optimizer='torch', max_grad_norm=None,
+        skip_nonfinite=False):
   """encoders: also train feature_net / feature_net_st (train.py:272-281: the maps are recomputed from the source images every iteration by
   the encoder's training form, the gradients of the maps flow on into its parameters, which sit in the optimizer with lrate_feature)."""
   if optimizer not in ('hip', 'torch'):
     raise ValueError(f'unknown optimizer {optimizer!r}: hip or torch')
+  guard = {k: v for k, v in (('max_grad_norm', max_grad_norm), ('skip_nonfinite', skip_nonfinite)) if v}
+  if guard and optimizer != 'hip':
+    raise ValueError('max_grad_norm / skip_nonfinite are arguments of dynibar_amd.optim.Adam.step: optimizer=\'hip\'')
   tc = TrainCase(dev, R=R, S=S)
   g = torch.Generator().manual_seed(9)
   batch = dict(tc.batch)
@@ -79,13 +86,16 @@ def run(dev='cuda:0', iters=40, R=1024, S=64, log_every=10, quiet=False, encoder
       else:
         loss = main_loss(ret, batch)
       loss.backward()
-      opt.step()
+      opt.step(**guard)
       if it % log_every == 0 or it == iters - 1:
         hist[stage].append(float(loss.detach()))
-        if not quiet:
-          print(f"{stage:9s} iteration {it:4d}  loss {float(loss.detach()):.5f}", flush=True)
+        if not quiet:  # (where the loop reads the loss back anyway is the place to read the guard's scalars)
+          norm = f'  gradient norm {opt.grad_stats.norm.item():.4g}' if guard else ''
+          print(f"{stage:9s} iteration {it:4d}  loss {float(loss.detach()):.5f}{norm}", flush=True)
     torch.cuda.synchronize()
     hist[stage + '_ms_per_iteration'] = (time.perf_counter() - t0) / iters * 1e3
+  if guard:
+    hist['grad_stats'] = {k: getattr(opt.grad_stats, k).item() for k in ('norm', 'coef', 'finite', 'calls', 'nonfinite')}
   return hist
 
 
@@ -96,7 +106,13 @@ if __name__ == '__main__':
     k = argv.index('--optimizer')
     which = argv[k + 1]
     del argv[k:k + 2]
+  max_grad_norm = None
+  if '--max-grad-norm' in argv:
+    k = argv.index('--max-grad-norm')
+    max_grad_norm = float(argv[k + 1])
+    del argv[k:k + 2]
   pos = [a for a in argv if not a.startswith('--')]
   it = int(pos[0]) if len(pos) > 0 else 40
   R = int(pos[1]) if len(pos) > 1 else 1024
-  print(json.dumps(run(iters=it, R=R, encoders='--encoders' in argv, optimizer=which)))
+  print(json.dumps(run(iters=it, R=R, encoders='--encoders' in argv, optimizer=which, max_grad_norm=max_grad_norm,
+                       skip_nonfinite='--skip-nonfinite' in argv)))
