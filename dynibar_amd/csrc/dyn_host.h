@@ -38,6 +38,7 @@ enum DynKernelSlot {
   DYN_K_SCENE_VIEWS, DYN_K_SCENE_SUPERVISION, DYN_K_FRAME_PACK, DYN_K_SCENE_VIEWS_MASKED, DYN_K_EVAL_MASK_PAIR, DYN_K_ADAM_STEP,
   DYN_K_RESIZE_AREA, DYN_K_RESIZE_LINEAR, DYN_K_RESIZE_NEAREST, DYN_K_ERODE_DISK, DYN_K_PERCENTILE_PAIR,
   DYN_K_GRAD_SUMSQ, DYN_K_GRAD_STATS, DYN_K_GRAD_SCALE, DYN_K_ADAM_STEP_GUARDED,
+  DYN_K_ADAMX_STEP, DYN_K_ADAMX_STEP_GUARDED, DYN_K_ADAM_ADVANCE,
   DYN_K_VIEWLOG_RANGES, DYN_K_VIEWLOG_FLOW_MAX, DYN_K_VIEWLOG_PANELS, DYN_K_COUNT
 };
 void dyn_prof_begin(int slot, hipStream_t stream);

@@ -267,6 +267,174 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_grad_scale(const DynAdamTensor
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The extended step (include/dynibar_hip.h states the contract): weight decay in both forms, amsgrad, maximize and step counts that live on
+// the device.  A body of its own over a record of its own, so k_adam_step and k_adam_step_guarded above keep their registers and their
+// five workgroups per CU; the grid, the chunk list, the path choice and the guard's way out are theirs.  What a tensor does not use costs
+// a wave-uniform branch (the record is read through wave-uniform loads): vmax is loaded and stored only where the record has one.
+//   k_adamx_step, k_adamx_step_guarded   amsgrad moves 36 bytes per element instead of 28 (vmax read and written); a full chunk then
+//                                        has twenty float4 loads in front of its first store.
+//   k_adam_advance                       one thread per record, after the step in stream order: the only writer of a tensor's step and
+//                                        pow.  The step kernels only read them, so no workgroup sees state another has advanced.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct AdamXScalars {
+  float a, s2, c1, c2, beta2, eps, wd, decay;
+  bool maximize, ams;
+};
+
+__device__ __forceinline__ void adamx_update(float& p, float g, float& m, float& v, float& vm, const float coef, const AdamXScalars& k) {
+  if (k.maximize) g = -g;
+  g = g * coef;
+  if (k.wd != 0.f) g = g + k.wd * p;
+  const float p1 = p * k.decay;
+  m = m + k.c1 * (g - m);
+  v = v * k.beta2 + (k.c2 * g) * g;
+  float d = v;
+  if (k.ams) {
+    vm = (v > vm) ? v : vm;
+    d = vm;
+  }
+  const float denom = sqrtf(d) / k.s2 + k.eps;
+  p = p1 + (k.a * m) / denom;
+}
+
+// coef is a compile-time 1 in the unguarded form: g * 1.0f folds away (it is the identity on every fp32 value the contract compares)
+template <bool GUARDED>
+__device__ __forceinline__ void adamx_update1(float& p, const float g, float& m, float& v, float& vm, const float coef, const AdamXScalars& k) {
+  adamx_update(p, g, m, v, vm, GUARDED ? coef : 1.0f, k);
+}
+template <bool GUARDED>
+__device__ __forceinline__ void adamx_update4(float4& p, const float4& g, float4& m, float4& v, float4& vm, const float coef, const AdamXScalars& k) {
+  adamx_update1<GUARDED>(p.x, g.x, m.x, v.x, vm.x, coef, k);
+  adamx_update1<GUARDED>(p.y, g.y, m.y, v.y, vm.y, coef, k);
+  adamx_update1<GUARDED>(p.z, g.z, m.z, v.z, vm.z, coef, k);
+  adamx_update1<GUARDED>(p.w, g.w, m.w, v.w, vm.w, coef, k);
+}
+
+template <bool GUARDED>
+__device__ __forceinline__ void adamx_step_chunk(const DynAdamXTensor* __restrict__ tensors, int n_tensors, const int2* __restrict__ chunks,
+                                                 int n_chunks, int zero_grads, const DynGradStats* __restrict__ stats, int skip_nonfinite) {
+  const int c = blockIdx.x, tid = threadIdx.x;
+  if (c >= n_chunks) return;
+  const int2 ch = chunks[c];
+  if (ch.x < 0 || ch.x >= n_tensors || ch.y < 0) return;
+  const DynAdamXTensor* __restrict__ t = tensors + ch.x;
+  const long n = t->n;
+  const long start = (long)ch.y * DYN_ADAM_CHUNK;
+  if (t->skip || start >= n) return;
+  const long left = n - start;
+  const int len = left < DYN_ADAM_CHUNK ? (int)left : DYN_ADAM_CHUNK;
+  float* p = t->p + start;
+  float* g = t->g + start;
+  float* m = t->m + start;
+  float* v = t->v + start;
+  float coef = 1.f;
+  if constexpr (GUARDED) {
+    coef = stats->coef;
+    if (skip_nonfinite && stats->finite == 0) {  // a held step: p, m, v and vmax stay as they are (k_adam_advance holds step and pow)
+      if (zero_grads)
+        for (int e = tid; e < len; e += ADAM_THREADS) g[e] = 0.f;
+      return;
+    }
+  }
+  AdamXScalars k;
+  k.a = t->a; k.s2 = t->s2; k.c1 = t->c1; k.c2 = t->c2; k.beta2 = t->beta2; k.eps = t->eps; k.wd = t->wd; k.decay = t->decay;
+  k.maximize = (t->flags & 1) != 0;
+  k.ams = t->vmax != nullptr;
+  if (const double* pw = t->pow) {  // the tensor's own step count lives on the device: the scalars of step t + 1 from beta^t, in double
+    const double b1 = pw[0] * t->beta1_d;
+    const double b2 = pw[1] * t->beta2_d;
+    k.a = (float)(-t->lr_d / (1.0 - b1));
+    k.s2 = (float)sqrt(1.0 - b2);
+  }
+  float* x = k.ams ? t->vmax + start : v;  // (without amsgrad x is never read or written; v keeps the alignment test what it was)
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                         reinterpret_cast<uintptr_t>(x);
+  if ((bits & 15) != 0) {
+    for (int e = tid; e < len; e += ADAM_THREADS) {
+      float pe = p[e], me = m[e], ve = v[e], xe = 0.f;
+      if (k.ams) xe = x[e];
+      adamx_update1<GUARDED>(pe, g[e], me, ve, xe, coef, k);
+      p[e] = pe; m[e] = me; v[e] = ve;
+      if (k.ams) x[e] = xe;
+      if (zero_grads) g[e] = 0.f;
+    }
+    return;
+  }
+  float4* p4 = reinterpret_cast<float4*>(p);
+  float4* g4 = reinterpret_cast<float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  float4* x4 = reinterpret_cast<float4*>(x);
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (len == DYN_ADAM_CHUNK) {  // a full chunk: the loads of all four rounds come before the first store
+    float4 pp[ADAM_ROUNDS], gg[ADAM_ROUNDS], mm[ADAM_ROUNDS], vv[ADAM_ROUNDS], xx[ADAM_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ADAM_ROUNDS; ++r) {
+      const int i = r * ADAM_THREADS + tid;
+      pp[r] = p4[i]; gg[r] = g4[i]; mm[r] = m4[i]; vv[r] = v4[i];
+      xx[r] = zero;
+      if (k.ams) xx[r] = x4[i];
+    }
+#pragma unroll
+    for (int r = 0; r < ADAM_ROUNDS; ++r) {
+      const int i = r * ADAM_THREADS + tid;
+      adamx_update4<GUARDED>(pp[r], gg[r], mm[r], vv[r], xx[r], coef, k);
+      p4[i] = pp[r]; m4[i] = mm[r]; v4[i] = vv[r];
+      if (k.ams) x4[i] = xx[r];
+      if (zero_grads) g4[i] = zero;
+    }
+    return;
+  }
+  const int n4 = len >> 2;
+  for (int i = tid; i < n4; i += ADAM_THREADS) {
+    float4 pe = p4[i], me = m4[i], ve = v4[i], xe = zero;
+    if (k.ams) xe = x4[i];
+    adamx_update4<GUARDED>(pe, g4[i], me, ve, xe, coef, k);
+    p4[i] = pe; m4[i] = me; v4[i] = ve;
+    if (k.ams) x4[i] = xe;
+    if (zero_grads) g4[i] = zero;
+  }
+  for (int e = 4 * n4 + tid; e < len; e += ADAM_THREADS) {  // the last 1..3 elements of the tensor
+    float pe = p[e], me = m[e], ve = v[e], xe = 0.f;
+    if (k.ams) xe = x[e];
+    adamx_update1<GUARDED>(pe, g[e], me, ve, xe, coef, k);
+    p[e] = pe; m[e] = me; v[e] = ve;
+    if (k.ams) x[e] = xe;
+    if (zero_grads) g[e] = 0.f;
+  }
+}
+
+// grid n_chunks, block ADAM_THREADS
+__global__ __launch_bounds__(ADAM_THREADS) void k_adamx_step(const DynAdamXTensor* __restrict__ tensors, int n_tensors, const int2* __restrict__ chunks,
+                                                             int n_chunks, int zero_grads) {
+  adamx_step_chunk<false>(tensors, n_tensors, chunks, n_chunks, zero_grads, nullptr, 0);
+}
+
+// grid n_chunks, block ADAM_THREADS
+__global__ __launch_bounds__(ADAM_THREADS) void k_adamx_step_guarded(const DynAdamXTensor* __restrict__ tensors, int n_tensors,
+                                                                     const int2* __restrict__ chunks, int n_chunks, int zero_grads,
+                                                                     const DynGradStats* __restrict__ stats, int skip_nonfinite) {
+  adamx_step_chunk<true>(tensors, n_tensors, chunks, n_chunks, zero_grads, stats, skip_nonfinite);
+}
+
+// grid cdiv(n_tensors, ADAM_THREADS), block ADAM_THREADS.  stats may be null (the unguarded step: nothing is ever held).
+__global__ __launch_bounds__(ADAM_THREADS) void k_adam_advance(const DynAdamXTensor* __restrict__ tensors, int n_tensors,
+                                                               const DynGradStats* __restrict__ stats, int skip_nonfinite) {
+  const int i = blockIdx.x * ADAM_THREADS + threadIdx.x;
+  if (i >= n_tensors) return;
+  if (stats != nullptr && skip_nonfinite && stats->finite == 0) return;
+  const DynAdamXTensor* t = tensors + i;
+  double* pw = t->pow;
+  float* step = t->step;
+  if (t->skip || pw == nullptr || step == nullptr) return;
+  const double b1 = pw[0] * t->beta1_d;
+  const double b2 = pw[1] * t->beta2_d;
+  *step = *step + 1.0f;
+  pw[0] = b1;
+  pw[1] = b2;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------
 // what every entry point here refuses about the records and the chunk list
@@ -322,5 +490,35 @@ extern "C" int dyn_adam_step_guarded(const DynAdamGuardedParams* p, void* stream
   DYN_LAUNCH(DYN_K_ADAM_STEP_GUARDED, who, k_adam_step_guarded, dim3((unsigned)p->n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream,
              static_cast<const DynAdamTensor*>(p->tensors), p->n_tensors, reinterpret_cast<const int2*>(p->chunks), p->n_chunks,
              p->zero_grads ? 1 : 0, p->stats, p->skip_nonfinite ? 1 : 0);
+  return 0;
+}
+
+// k_adam_advance after an extended step, in stream order; stats null for the unguarded step
+static int adam_advance(const char* who, const void* tensors, int n_tensors, const DynGradStats* stats, int skip_nonfinite, hipStream_t stream) {
+  DYN_LAUNCH(DYN_K_ADAM_ADVANCE, who, k_adam_advance, dim3((unsigned)((n_tensors + ADAM_THREADS - 1) / ADAM_THREADS)), dim3(ADAM_THREADS), 0, stream,
+             static_cast<const DynAdamXTensor*>(tensors), n_tensors, stats, skip_nonfinite);
+  return 0;
+}
+
+extern "C" int dyn_adamx_step(const DynAdamXParams* p, void* stream) {
+  const char* who = "dyn_adamx_step";
+  DYN_REQUIRE(p, "%s: null params", who);
+  if (const int rc = adam_tables_ok(who, p->tensors, p->n_tensors, p->chunks, p->n_chunks)) return rc;
+  DYN_LAUNCH(DYN_K_ADAMX_STEP, who, k_adamx_step, dim3((unsigned)p->n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream,
+             static_cast<const DynAdamXTensor*>(p->tensors), p->n_tensors, reinterpret_cast<const int2*>(p->chunks), p->n_chunks, p->zero_grads ? 1 : 0);
+  if (p->advance) return adam_advance(who, p->tensors, p->n_tensors, nullptr, 0, (hipStream_t)stream);
+  return 0;
+}
+
+extern "C" int dyn_adamx_step_guarded(const DynAdamXGuardedParams* p, void* stream) {
+  const char* who = "dyn_adamx_step_guarded";
+  DYN_REQUIRE(p, "%s: null params", who);
+  if (const int rc = adam_tables_ok(who, p->tensors, p->n_tensors, p->chunks, p->n_chunks)) return rc;
+  DYN_REQUIRE(p->stats, "%s: stats is required", who);
+  DYN_REQUIRE((reinterpret_cast<uintptr_t>(p->stats) & 7) == 0, "%s: stats must start on 8 bytes", who);
+  DYN_LAUNCH(DYN_K_ADAMX_STEP_GUARDED, who, k_adamx_step_guarded, dim3((unsigned)p->n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream,
+             static_cast<const DynAdamXTensor*>(p->tensors), p->n_tensors, reinterpret_cast<const int2*>(p->chunks), p->n_chunks,
+             p->zero_grads ? 1 : 0, p->stats, p->skip_nonfinite ? 1 : 0);
+  if (p->advance) return adam_advance(who, p->tensors, p->n_tensors, p->stats, p->skip_nonfinite ? 1 : 0, (hipStream_t)stream);
   return 0;
 }

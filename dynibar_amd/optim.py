@@ -23,16 +23,32 @@ L2 norm of every gradient of every group (double sums in a fixed order), the cli
 ``skip_nonfinite`` leaves p, exp_avg and exp_avg_sq untouched when one is not (``zero_grads`` still clears).  Still one host-to-device copy,
 nothing back, no synchronisation, no allocation after the first step; ``.grad`` is never rewritten with the clipped values.  The arithmetic
 is a contract as well (include/dynibar_hip.h).  Without the two arguments ``step()`` is the one ``k_adam_step`` launch it always was.
-STEP COUNTS: the per-parameter ``step`` lives on the host, and the host cannot know whether the device skipped without a synchronisation, so
-``step`` advances for every parameter that had a gradient, skipped or not: a skipped step still counts towards the bias correction.  What
-the device saw is in ``opt.grad_stats`` (None before the first guarded step): 0-d device tensor views ``norm``, ``coef``, ``finite``, ``calls``,
+STEP COUNTS, two behaviours.  ``capturable=False`` (the default): the per-parameter ``step`` lives on the host, and the host cannot know whether
+the device skipped without a synchronisation, so ``step`` advances for every parameter that had a gradient, skipped or not: a skipped step
+still counts towards the bias correction.  ``capturable=True``: ``step`` is a float32 0-d DEVICE tensor (torch's capturable layout) next to
+``beta_pow``, a float64 ``[beta1^t, beta2^t]`` device tensor of ours; the kernel forms the bias corrections from them in double and
+``k_adam_advance`` advances both after the step -- unless the step was held, which then leaves p, the moments, ``step`` and ``beta_pow`` bit for
+bit as they were: a run with a held step equals the run of its finite steps alone.  (``beta_pow`` is a running product: betas changed in
+mid-run continue from it, where torch would form ``beta ** step`` afresh.)  What the device saw is in ``opt.grad_stats`` (None before the first guarded step): 0-d device tensor views ``norm``, ``coef``, ``finite``, ``calls``,
 ``nonfinite`` (and ``sumsq``) into one small buffer that every guarded step overwrites; ``calls`` and ``nonfinite`` count guarded steps and those
 whose gradients were not finite since the parameter set last changed.  Reading one (``.item()``) is the caller's synchronisation -- where the
 loop prints is the natural place.
 ``grad_norm(parameters)`` and ``clip_grad_norm_(parameters, max_norm)`` are the same kernels for callers that keep torch's optimizer or want the
 scalar alone.
 
-Not built, refused by name: amsgrad, maximize, weight_decay, capturable, differentiable, an explicit foreach / fused.  Tensors must be
+THE OPTIONS of torch's constructor live in two further classes, ``AdamX`` (``torch.optim.Adam``'s whole constructor) and ``AdamW``
+(``torch.optim.AdamW``): ``weight_decay`` (coupled, or decoupled with ``decoupled_weight_decay=True`` / the ``AdamW`` class), ``amsgrad`` (state
+``max_exp_avg_sq``), ``maximize`` and ``capturable``.  ``Adam`` itself is what it was: it refuses these four by name and launches the plain kernels.
+An ``AdamX`` / ``AdamW`` none of whose groups sets one of them launches ``k_adam_step`` / ``k_adam_step_guarded`` exactly as ``Adam`` does; otherwise every group, whatever its options, goes through ONE launch of the extended kernel
+(``dyn_adamx_step`` / ``dyn_adamx_step_guarded``, a record and a contract of their own in include/dynibar_hip.h) plus the one-thread-per-tensor
+``k_adam_advance`` when a group is capturable.  Per element: g1 = -g under maximize; g2 = g1 coef under the guard; g3 = g2 + wd p (coupled);
+p1 = p decay with decay = fp32(1 - lr weight_decay) (decoupled); m, v as above on g3; vmax = v > vmax ? v : vmax and denom from vmax under
+amsgrad (a NaN v leaves vmax alone, the one difference from ``torch.maximum``; ``skip_nonfinite`` keeps NaN out); p = p1 + (a m) / denom.
+
+VISIBILITY: the kernels write the parameters through raw pointers, so after every step each stepped parameter's version counter is advanced
+(``torch._C._increment_version``, no launch): the packed inference weights, cached by ``(data_ptr, _version)``, are rebuilt by the next render.
+
+Not built, refused by name: differentiable, an explicit foreach / fused, a tensor lr, sparse gradients (and in ``Adam`` the four options above).  Tensors must be
 contiguous fp32 on ONE HIP device: there is no CPU fallback, host tensors are refused.
 """
 from __future__ import annotations
@@ -56,13 +72,18 @@ _NP_OF = {ctypes.c_void_p: '<u8', ctypes.c_int64: '<i8', ctypes.c_float: '<f4', 
 RECORD = np.dtype([(name, _NP_OF[ct]) for name, ct in _lib._STRUCT_SPECS['DynAdamTensor']])
 assert RECORD.itemsize == ctypes.sizeof(_lib.STRUCTS['DynAdamTensor']) and RECORD.itemsize % 8 == 0
 
+XRECORD = np.dtype([(name, _NP_OF[ct]) for name, ct in _lib._STRUCT_SPECS['DynAdamXTensor']])  # the record of the extended step
+assert XRECORD.itemsize == ctypes.sizeof(_lib.STRUCTS['DynAdamXTensor']) == 128 and RECORD.names[:-1] == XRECORD.names[:len(RECORD.names) - 1]
+
 STATS = np.dtype([(name, _NP_OF[ct]) for name, ct in _lib._STRUCT_SPECS['DynGradStats']])
 assert STATS.itemsize == ctypes.sizeof(_lib.STRUCTS['DynGradStats']) == 40 and all(STATS.fields[k][1] % STATS[k].itemsize == 0 for k in STATS.names)
 
 GradStats = collections.namedtuple('GradStats', 'norm coef finite calls nonfinite sumsq')
 GradStats.__doc__ = """What the last ``dyn_grad_norm`` over a table wrote (DynGradStats): 0-d device tensors that are VIEWS into the table's buffer."""
 
-_UNBUILT = ('amsgrad', 'maximize', 'capturable', 'differentiable')
+_UNBUILT = ('differentiable',)
+_EXTENDED = ('amsgrad', 'maximize', 'capturable')  # with weight_decay != 0: what sends a step through dyn_adamx_step
+_increment_version = getattr(torch._C, '_increment_version', None)
 _TORCH_HAS_DECOUPLED = 'decoupled_weight_decay' in inspect.signature(torch.optim.Adam.__init__).parameters
 
 
@@ -79,12 +100,13 @@ def _chunk_list(sizes):
                          for i, n in enumerate(sizes)] or [np.zeros((0, 2), np.int32)])
 
 
-def _new_tables(dev, sizes):
+def _new_tables(dev, sizes, extended=False):
   """What depends on a parameter set alone: the chunk list (uploaded once), the device buffer its records go to, the partial sums and the
-  zeroed DynGradStats of the guard."""
+  zeroed DynGradStats of the guard.  extended: the buffer holds the DynAdamTensor records (the norm reads them) and behind them the
+  DynAdamXTensor records of the same tensors, so a step is still one copy."""
   chunks = _chunk_list(sizes)
   host = torch.from_numpy(np.ascontiguousarray(chunks))
-  nbytes = max(1, len(sizes)) * RECORD.itemsize
+  nbytes = max(1, len(sizes)) * (RECORD.itemsize + (XRECORD.itemsize if extended else 0))
   if dev.type == 'cuda':
     with torch.cuda.device(dev):
       chunks_dev = host.pin_memory().to(dev, non_blocking=True) if len(chunks) else host.to(dev)
@@ -99,7 +121,7 @@ def _new_tables(dev, sizes):
   at = {k: STATS.fields[k][1] for k in STATS.names}
   views = GradStats(norm=f32[at['norm'] // 4], coef=f32[at['coef'] // 4], finite=i32[at['finite'] // 4], calls=stats[at['calls'] // 8],
                     nonfinite=stats[at['nonfinite'] // 8], sumsq=stats.view(torch.float64)[at['sumsq'] // 8])
-  return dict(device=dev, sizes=sizes, n_chunks=int(len(chunks)), chunks=chunks_dev, records=records_dev, nbytes=nbytes, partials=partials,
+  return dict(device=dev, sizes=sizes, extended=bool(extended), n_chunks=int(len(chunks)), chunks=chunks_dev, records=records_dev, nbytes=nbytes, partials=partials,
               stats=stats, grad_stats=views)
 
 
@@ -136,15 +158,35 @@ def _check_max_norm(value, who, what):
   return value
 
 
+def _written(tensors):
+  """A kernel wrote these tensors through their raw pointers: advance their version counters, as an in-place torch op would have, so that
+  whatever is cached by (data_ptr, _version) -- the packed inference weights -- is rebuilt.  No launch."""
+  if not tensors:
+    return
+  if _increment_version is None:
+    for t in tensors:
+      t.add_(0)
+    return
+  try:
+    _increment_version(tensors)
+  except TypeError:  # (a torch whose helper takes one tensor)
+    for t in tensors:
+      _increment_version(t)
+
+
 def _name(gi, pi, p):
   return f'parameter {pi} of group {gi} {tuple(p.shape)}'
 
 
-class Adam(torch.optim.Optimizer):
-  """``torch.optim.Adam(params, lr, betas, eps)`` with the whole update in one HIP launch (module docstring)."""
+class AdamX(torch.optim.Optimizer):
+  """``torch.optim.Adam(params, lr, betas, eps, weight_decay, amsgrad, maximize=, capturable=, decoupled_weight_decay=)``, the whole constructor, with
+  the whole update in one HIP launch (module docstring).  ``extended_kernel = True`` sends every step through ``dyn_adamx_step`` even when no
+  group asks for one of its options (A/B tests and tools/optimbench.py)."""
+
+  extended_kernel = False
 
   def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None, maximize=False,
-               capturable=False, differentiable=False, fused=None):
+               capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
     if isinstance(lr, torch.Tensor):
       raise ValueError('dynibar_amd.optim.Adam: lr must be a number, a tensor lr is not built')
     if not 0.0 <= lr:
@@ -155,12 +197,14 @@ class Adam(torch.optim.Optimizer):
       raise ValueError(f'Invalid beta parameter at index 0: {betas[0]}')
     if not 0.0 <= betas[1] < 1.0:
       raise ValueError(f'Invalid beta parameter at index 1: {betas[1]}')
+    if not 0.0 <= weight_decay:
+      raise ValueError(f'Invalid weight_decay value: {weight_decay}')
     if foreach is not None or fused is not None:
       raise NotImplementedError('dynibar_amd.optim.Adam: foreach / fused choose among torch\'s implementations; this optimizer has one kernel')
     defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None,
                     capturable=capturable, differentiable=differentiable, fused=None)
-    if _TORCH_HAS_DECOUPLED:
-      defaults['decoupled_weight_decay'] = False
+    if _TORCH_HAS_DECOUPLED or decoupled_weight_decay:
+      defaults['decoupled_weight_decay'] = bool(decoupled_weight_decay)
     self._tables = None     # what depends on the parameter set alone: sizes, the chunk list on the device, the device buffer of the records
     self._staging = []      # pinned host buffers of the records with the event of their last copy
     self._cleared = {}      # id(parameter) -> (gradient tensor, its version) as the last step(zero_grads=True) left it
@@ -173,8 +217,9 @@ class Adam(torch.optim.Optimizer):
     for opt in _UNBUILT:
       if group.get(opt, False):
         raise NotImplementedError(f'dynibar_amd.optim.Adam: {opt}=True (group {gi}) is not built')
-    if group.get('weight_decay', 0) != 0:
-      raise NotImplementedError(f'dynibar_amd.optim.Adam: weight_decay={group["weight_decay"]} (group {gi}) is not built; the reference trains with 0')
+    wd = group.get('weight_decay', 0)
+    if isinstance(wd, torch.Tensor) or not 0.0 <= wd:
+      raise ValueError(f'dynibar_amd.optim.Adam: weight_decay of group {gi} must be a number >= 0, got {wd!r}')
     if group.get('foreach') is not None or group.get('fused') is not None:
       raise NotImplementedError(f'dynibar_amd.optim.Adam: foreach / fused (group {gi}) choose among torch\'s implementations; this optimizer has one kernel')
     if isinstance(group['lr'], torch.Tensor):
@@ -199,7 +244,41 @@ class Adam(torch.optim.Optimizer):
       for p in group['params']:
         st = self.state.get(p, [])
         if len(st) != 0 and not torch.is_tensor(st['step']):  # torch <= 1.11 kept a Python int (torch.optim.Adam.__setstate__)
-          st['step'] = torch.tensor(float(st['step']), dtype=torch.float32)
+          st['step'] = torch.tensor(float(st['step']), dtype=torch.float32, device=p.device if group['capturable'] else 'cpu')
+
+  def load_state_dict(self, state_dict):
+    """torch's, then the device-resident step counts of capturable groups: torch's loader casts every state tensor except ``step`` to the
+    parameter's dtype, so ``beta_pow`` (float64 ``[beta1^t, beta2^t]``) is taken from the checkpoint itself, bit for bit.  A checkpoint without
+    it -- one that ``torch.optim.Adam`` / ``AdamW`` saved -- gets ``[beta1 ** t, beta2 ** t]`` formed here on the host in double from the
+    checkpoint's ``step`` and uploaded once (reading a device ``step`` is the one synchronisation of a load).  Groups that are not capturable
+    carry no ``beta_pow``."""
+    super().load_state_dict(state_dict)
+    saved_ids = [i for g in state_dict['param_groups'] for i in g['params']]
+    mine = [(g, p) for g in self.param_groups for p in g['params']]
+    for pid, (group, p) in zip(saved_ids, mine):
+      st = self.state.get(p)
+      if not st:
+        continue
+      if not group['capturable']:
+        st.pop('beta_pow', None)
+        continue
+      saved = state_dict['state'].get(pid, {}).get('beta_pow')
+      if torch.is_tensor(saved) and saved.dtype == torch.float64 and saved.numel() == 2:
+        st['beta_pow'] = saved.detach().reshape(2).to(p.device, copy=True)
+      else:
+        st.pop('beta_pow', None)
+        self._device_counts(st, p, group)
+
+  @staticmethod
+  def _device_counts(st, p, group):
+    """capturable: ``step`` a float32 0-d tensor and ``beta_pow`` float64 [2] on the parameter's device (made from the host's count where missing)"""
+    step, pw = st['step'], st.get('beta_pow')
+    if not (torch.is_tensor(pw) and pw.dtype == torch.float64 and pw.shape == (2,) and pw.device == p.device and pw.is_contiguous()):
+      t = float(step)
+      beta1, beta2 = group['betas']
+      st['beta_pow'] = torch.tensor([beta1 ** t, beta2 ** t], dtype=torch.float64).to(p.device)
+    if step.device != p.device or step.dtype != torch.float32 or step.dim() != 0:
+      st['step'] = step.detach().to(device=p.device, dtype=torch.float32).reshape(())
 
   def zero_grad(self, set_to_none=True):
     """torch's, except that ``set_to_none=False`` does not clear again what ``step(zero_grads=True)`` has cleared and nothing has written since."""
@@ -225,6 +304,7 @@ class Adam(torch.optim.Optimizer):
     entries, dev = [], None
     for gi, group in enumerate(self.param_groups):
       self._check_group(group, gi)
+      moments = ('exp_avg', 'exp_avg_sq', 'max_exp_avg_sq') if group.get('amsgrad', False) else ('exp_avg', 'exp_avg_sq')
       for pi, p in enumerate(group['params']):
         if p.dtype != torch.float32:
           raise TypeError(f'dynibar_amd.optim.Adam: {_name(gi, pi, p)} is {str(p.dtype).replace("torch.", "")}; the kernel updates float32 only')
@@ -245,8 +325,8 @@ class Adam(torch.optim.Optimizer):
                              f'its parameter is on {p.device}')
           st = self.state.get(p)
           if st:
-            for key in ('exp_avg', 'exp_avg_sq'):
-              m = st[key]
+            for key in moments:
+              m = st[key] if key != 'max_exp_avg_sq' else st.get(key, st['exp_avg_sq'])  # (made by the step where a checkpoint lacks it)
               if m.dtype != torch.float32 or m.shape != p.shape or m.device != p.device or not m.is_contiguous():
                 raise ValueError(f'dynibar_amd.optim.Adam: {key} of {_name(gi, pi, p)} must be contiguous float32 {tuple(p.shape)} on {p.device}, '
                                  f'got {str(m.dtype).replace("torch.", "")} {tuple(m.shape)} on {m.device}')
@@ -261,11 +341,11 @@ class Adam(torch.optim.Optimizer):
           raise RuntimeError(f'dynibar_amd.optim.Adam: parameters on more than one device: {_name(gi, pi, p)} is on {p.device}, others on {dev} (one HIP device)')
     return dev, entries
 
-  def _make_tables(self, dev, sizes):
+  def _make_tables(self, dev, sizes, extended=False):
     """The chunk list of a parameter set (uploaded once), the device buffer its records go to and the guard's buffers."""
     self._staging = []
     self._grad_stats = None
-    self._tables = _new_tables(dev, sizes)
+    self._tables = _new_tables(dev, sizes, extended)
 
   def _stage(self, dev, nbytes):
     return _stage_in(self._staging, dev, nbytes)
@@ -291,61 +371,134 @@ class Adam(torch.optim.Optimizer):
     if dev is None or all(g is None for _, _, g in entries):
       return loss
     sizes = [p.numel() for _, p, _ in entries]
-    if self._tables is None or self._tables['device'] != dev or self._tables['sizes'] != sizes:
-      self._make_tables(dev, sizes)
+    # the plain kernels unless a group asks for what only the extended step has: defaults change nothing
+    extended = bool(self.extended_kernel) or any(g.get('weight_decay', 0) != 0 or any(g.get(o, False) for o in _EXTENDED) for g in self.param_groups)
+    if self._tables is None or self._tables['device'] != dev or self._tables['sizes'] != sizes or self._tables['extended'] != extended:
+      self._make_tables(dev, sizes, extended)
     tab = self._tables
     if tab['n_chunks'] == 0:
       return loss
     n = len(entries)
-    ptr = {k: [0] * n for k in 'pgmv'}
-    a, s2, c1, c2, b2, ep = ([0.0] * n for _ in range(6))
-    skip = [1] * n
-    scalars, copies, cleared = {}, [], {}
+    ptr = {k: [0] * n for k in (('p', 'g', 'm', 'v', 'vmax', 'pow', 'step') if extended else 'pgmv')}
+    a, s2, skip = [0.0] * n, [0.0] * n, [1] * n
+    scalars, copies, cleared, stepped, advance = {}, [], {}, [], 0
+    per_group, consts = [], []  # what a group's options come to, once per step and not once per tensor
+    for group in self.param_groups:
+      lr, (beta1, beta2), lam = group['lr'], group['betas'], group.get('weight_decay', 0)
+      decoupled = lam != 0 and bool(group.get('decoupled_weight_decay', False))
+      per_group.append((group, lr, beta1, beta2, bool(group.get('capturable', False)), bool(group.get('amsgrad', False))))
+      # c1, c2, beta2, eps; wd, decay (the factor in double here, fp32 in the record: rounded once), flags; lr, beta1, beta2 for the device's scalars
+      consts.append((1 - beta1, 1 - beta2, beta2, group['eps'], 0.0 if decoupled else lam, 1 - lr * lam if decoupled else 1.0,
+                     1 if group.get('maximize', False) else 0, lr, beta1, beta2))
     for i, (gi, p, g) in enumerate(entries):
       if g is None or sizes[i] == 0:
         continue
-      group = self.param_groups[gi]
+      group, lr, beta1, beta2, capturable, amsgrad = per_group[gi]
       st = self.state[p]
       if len(st) == 0:  # torch's layout of a first-seen parameter
-        st['step'] = torch.tensor(0.0, dtype=torch.float32)
+        st['step'] = torch.zeros((), dtype=torch.float32, device=p.device) if capturable else torch.tensor(0.0, dtype=torch.float32)
         st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
         st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-      st['step'] += 1
-      lr, (beta1, beta2), eps = group['lr'], group['betas'], group['eps']
-      key = (lr, beta1, beta2, st['step'].item())
-      if key not in scalars:
-        scalars[key] = step_scalars(*key)
+      if capturable:  # the count lives on the device: k_adam_advance is its only writer, a held step leaves it alone
+        self._device_counts(st, p, group)
+        ptr['pow'][i], ptr['step'][i] = st['beta_pow'].data_ptr(), st['step'].data_ptr()
+        advance = 1
+      else:
+        step = st['step']
+        if step.is_cuda:  # (a group switched back from capturable: one synchronisation)
+          step = st['step'] = step.detach().cpu()
+        step += 1
+        key = (lr, beta1, beta2, step.item())
+        if key not in scalars:
+          scalars[key] = step_scalars(*key)
+        a[i], s2[i] = scalars[key]
+      if amsgrad:
+        if 'max_exp_avg_sq' not in st:
+          st['max_exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        ptr['vmax'][i] = st['max_exp_avg_sq'].data_ptr()
       gc = g if g.is_contiguous() else g.contiguous()
       if gc is not g:
         copies.append((g, gc))  # (kept alive until the launch is enqueued; cleared below when the kernel clears its copy)
       ptr['p'][i], ptr['g'][i], ptr['m'][i], ptr['v'][i] = p.data_ptr(), gc.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr()
-      a[i], s2[i] = scalars[key]
-      c1[i], c2[i], b2[i], ep[i] = 1 - beta1, 1 - beta2, beta2, eps
       skip[i] = 0
+      stepped.append(p)
       if zero_grads:
         cleared[id(p)] = g
     host, event = self._stage(dev, tab['nbytes'])
     rec = host.numpy()[:n * RECORD.itemsize].view(RECORD)
     for k in 'pgmv':
       rec[k] = ptr[k]
-    rec['n'], rec['a'], rec['s2'], rec['c1'], rec['c2'], rec['beta2'], rec['eps'], rec['skip'], rec['reserved'] = sizes, a, s2, c1, c2, b2, ep, skip, 0
+    const = np.array(consts, np.float64)[[gi for gi, _, _ in entries]]  # [n, 10]: each tensor's group constants
+    rec['n'], rec['a'], rec['s2'], rec['skip'], rec['reserved'] = sizes, a, s2, skip, 0
+    rec['c1'], rec['c2'], rec['beta2'], rec['eps'] = const[:, 0], const[:, 1], const[:, 2], const[:, 3]
+    if extended:
+      xrec = host.numpy()[n * RECORD.itemsize:n * (RECORD.itemsize + XRECORD.itemsize)].view(XRECORD)
+      for k in RECORD.names[:-1]:
+        xrec[k] = rec[k]
+      for k in ('vmax', 'pow', 'step'):
+        xrec[k] = ptr[k]
+      xrec['wd'], xrec['decay'], xrec['flags'], xrec['lr_d'], xrec['beta1_d'], xrec['beta2_d'] = (const[:, j] for j in range(4, 10))
     records = _send(tab, host, event, dev)
     like = entries[0][1]
     table = dict(tensors=ctypes.c_void_p(records.data_ptr()), n_tensors=n, chunks=ctypes.c_void_p(tab['chunks'].data_ptr()), n_chunks=tab['n_chunks'])
+    xtable = dict(table, tensors=ctypes.c_void_p(records.data_ptr() + n * RECORD.itemsize), zero_grads=1 if zero_grads else 0, advance=advance)
     if guarded:
       stats = ctypes.c_void_p(tab['stats'].data_ptr())
       call('dyn_grad_norm', params('DynGradNormParams', partials=ctypes.c_void_p(tab['partials'].data_ptr()), stats=stats,
                                    max_norm=0.0 if max_grad_norm is None else max_grad_norm, count=1, **table), stream_of(like))
-      call('dyn_adam_step_guarded', params('DynAdamGuardedParams', zero_grads=1 if zero_grads else 0, skip_nonfinite=1 if skip_nonfinite else 0,
-                                           stats=stats, **table), stream_of(like))
+      if extended:
+        call('dyn_adamx_step_guarded', params('DynAdamXGuardedParams', skip_nonfinite=1 if skip_nonfinite else 0, stats=stats, **xtable), stream_of(like))
+      else:
+        call('dyn_adam_step_guarded', params('DynAdamGuardedParams', zero_grads=1 if zero_grads else 0, skip_nonfinite=1 if skip_nonfinite else 0,
+                                             stats=stats, **table), stream_of(like))
       self._grad_stats = tab['grad_stats']
+    elif extended:
+      call('dyn_adamx_step', params('DynAdamXParams', **xtable), stream_of(like))
     else:
       call('dyn_adam_step', params('DynAdamParams', zero_grads=1 if zero_grads else 0, **table), stream_of(like))
+    _written(stepped)  # the kernel wrote the parameters through raw pointers
     if zero_grads:
       for g, _ in copies:  # the kernel cleared the contiguous copy, not the strided gradient itself
         g.zero_()
       self._cleared = {k: (g, g._version) for k, g in cleared.items()}
     return loss
+
+
+class Adam(AdamX):
+  """``torch.optim.Adam(params, lr, betas, eps)`` with the whole update in one HIP launch: the optimizer of the reference's training loop, as it
+  was before ``AdamX``.  It keeps refusing ``amsgrad``, ``maximize``, ``capturable`` and ``weight_decay != 0`` by name -- a script that sets one of
+  them changes its class to ``AdamX`` (or ``AdamW``) in the same line -- and always launches the plain kernels."""
+
+  def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None, maximize=False,
+               capturable=False, differentiable=False, fused=None):
+    super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                     differentiable=differentiable, fused=fused)
+
+  @staticmethod
+  def _check_group(group, gi):
+    for opt in _EXTENDED + _UNBUILT:
+      if group.get(opt, False):
+        raise NotImplementedError(f'dynibar_amd.optim.Adam: {opt}=True (group {gi}) is not built' +
+                                  (' in this class; dynibar_amd.optim.AdamX has it' if opt in _EXTENDED else ''))
+    if group.get('weight_decay', 0) != 0:
+      raise NotImplementedError(f'dynibar_amd.optim.Adam: weight_decay={group["weight_decay"]} (group {gi}) is not built in this class; '
+                                'dynibar_amd.optim.AdamX (coupled) and AdamW (decoupled) have it')
+    AdamX._check_group(group, gi)
+
+
+class AdamW(AdamX):
+  """``torch.optim.AdamW``: ``AdamX`` with ``decoupled_weight_decay=True`` and torch's default ``weight_decay=1e-2`` -- the parameter is multiplied by
+  ``fp32(1 - lr * weight_decay)`` and the moments never see the decay.  Its ``state_dict`` loads into ``torch.optim.AdamW`` and back."""
+
+  def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+               capturable=False, differentiable=False, fused=None):
+    super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                     differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
+
+  def __setstate__(self, state):
+    super().__setstate__(state)
+    for group in self.param_groups:
+      group['decoupled_weight_decay'] = True  # (torch.optim.AdamW.__setstate__ does the same: a group of an AdamW is always decoupled)
 
 
 # ---- the norm and the clip on their own ----------------------------------------------------------------------------------------------

@@ -929,6 +929,69 @@ typedef struct {
 } DynAdamGuardedParams;
 int dyn_adam_step_guarded(const DynAdamGuardedParams* p, void* stream);
 
+/* ------ the extended step: weight decay (coupled and decoupled), amsgrad, maximize, device-resident step counts -------------------------
+ * dyn_adam_step and dyn_adam_step_guarded above are what they were; a caller none of whose tensors needs an option below keeps calling them.
+ * The extended step has its own record, DynAdamXTensor, its own kernels (k_adamx_step, k_adamx_step_guarded: the grid, the chunk list, the
+ * float4 / single-float choice -- vmax joins the alignment test when it is not null --, zero_grads and the guard's wave-uniform way out of
+ * the kernels above) and one more kernel, k_adam_advance.  Per element, fp32, every operation rounded once (no fma), division and square
+ * root correctly rounded, subnormals kept, in this order:
+ *     g1 = (flags & 1) ? -g : g                                    maximize
+ *     g2 = g1 * coef                                               the guarded form only (coef == 1 is the identity)
+ *     g3 = (wd != 0) ? g2 + (wd * p) : g2                          coupled decay: two roundings; wd == 0 adds nothing (not even +0)
+ *     p1 = p * decay                                               decoupled decay, decay = fp32(1 - lr * lambda) formed by the host in double;
+ *                                                                  decay == 1 is the identity.  The moments see the undecayed gradient g3 and
+ *                                                                  the coupled term reads the undecayed p, as in torch's AdamW / Adam.
+ *     m = m + c1 * (g3 - m)          v = v * beta2 + (c2 * g3) * g3
+ *     vmax != null:  vmax = (v > vmax) ? v : vmax,  d = vmax       amsgrad; otherwise d = v.  A NaN v leaves vmax as it is, where
+ *                                                                  torch.maximum would store the NaN: the only difference from torch's
+ *                                                                  amsgrad, and skip_nonfinite is what keeps NaN out of v in the first place.
+ *     denom = sqrtf(d) / s2 + eps    p = p1 + (a * m) / denom
+ * The guard's norm (dyn_grad_norm, over DynAdamTensor records of the same tensors) is taken over the raw gradients g, as clip_grad_norm_ in
+ * front of a torch step would.
+ * Device-resident step counts: a record with pow != null takes a and s2 from the device instead of the record.  pow[0], pow[1] hold
+ * beta1^t, beta2^t of the t steps the tensor has taken (1.0, 1.0 before the first), step holds t as fp32.  Every workgroup of the tensor
+ * forms, in double, every operation rounded once,
+ *     b1 = pow[0] * beta1_d     b2 = pow[1] * beta2_d     a = (float)(-lr_d / (1.0 - b1))     s2 = (float)sqrt(1.0 - b2)
+ * and only reads that state.  k_adam_advance (one thread per record, launched after the step in stream order when advance != 0) then
+ * stores step + 1.0f, b1 and b2 for every record with pow != null and skip == 0 -- unless the step was held (skip_nonfinite != 0 and
+ * finite == 0), which leaves p, m, v, vmax, step and pow bit for bit as they were.  No workgroup reads state another one has written in
+ * the same launch; nothing is read back by the host.
+ * Refused before a launch, DYN_E_INVALID: what dyn_adam_step / dyn_adam_step_guarded refuse. */
+typedef struct {
+  float *p, *g, *m, *v;        /* as DynAdamTensor */
+  int64_t n;
+  float a, s2;                 /* read when pow == null */
+  float c1, c2, beta2, eps;
+  int32_t skip;
+  int32_t flags;               /* bit 0: maximize */
+  float* vmax;                 /* DEVICE fp32 [n], null: no amsgrad */
+  float wd;                    /* the coupled lambda, 0: none */
+  float decay;                 /* the decoupled factor, 1: none */
+  double* pow;                 /* DEVICE [2], 8-byte aligned, null: a and s2 above.  Read by the step, written by k_adam_advance alone */
+  float* step;                 /* DEVICE fp32 scalar, required with pow.  Written by k_adam_advance alone */
+  double lr_d, beta1_d, beta2_d; /* read with pow */
+} DynAdamXTensor;
+typedef struct {
+  const void* tensors;         /* DEVICE [n_tensors] DynAdamXTensor, 8-byte aligned */
+  int n_tensors;
+  const int32_t* chunks;       /* as for dyn_adam_step */
+  int n_chunks;
+  int zero_grads;
+  int advance;                 /* != 0: some record has pow != null, k_adam_advance follows the step */
+} DynAdamXParams;
+int dyn_adamx_step(const DynAdamXParams* p, void* stream);
+typedef struct {
+  const void* tensors;
+  int n_tensors;
+  const int32_t* chunks;
+  int n_chunks;
+  int zero_grads;
+  int advance;
+  int skip_nonfinite;
+  const DynGradStats* stats;   /* DEVICE: coef and finite are read */
+} DynAdamXGuardedParams;
+int dyn_adamx_step_guarded(const DynAdamXGuardedParams* p, void* stream);
+
 /* ====== scene preparation (save_monocular_cameras.py:90-113, monocular.py:125-204, eval_nvidia.py:387-428) ====================================
  * The resizes the reference takes from cv2, the erosion it takes from skimage and np.percentile of a depth map, on B images per launch.
  * The contracts restate OpenCV's and skimage's algorithms; whether they agree with the real libraries is BELIEVED, NOT VERIFIED.

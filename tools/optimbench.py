@@ -1,7 +1,7 @@
 """The optimizer step on the kid-running model's parameter set: dynibar_amd.optim.Adam (one k_adam_step launch) against torch.optim.Adam, in one
 process on the same gradients.  GPU only -- there is no CPU path.
 
-  python tools/optimbench.py [--rounds 30] [--inner 20] [--out profiles/optimizer.txt]
+  python tools/optimbench.py [--rounds 30] [--inner 20] [--out profiles/optimizer.txt] [--weight-decay L] [--adamw] [--amsgrad] [--maximize] [--capturable]
 
 The parameter set is the model's (ibrnet/model.py:341-364): the static and the dynamic MLP, the motion MLP (shapes of dynibar_amd.synthetic's layer
 tables), the two ResNet encoders (its encoder weights) and the trajectory basis, in the reference's six groups with its four learning rates
@@ -16,7 +16,10 @@ The guard (step(max_grad_norm=..., skip_nonfinite=True): k_grad_sumsq, k_grad_st
 so the four legs above keep their layout: the guarded step twice (the spread of two identical legs), torch.nn.utils.clip_grad_norm_ followed by
 torch.optim.Adam.step() on the same gradients, and optim.grad_norm alone.  The legs share their gradient tensors, so max_norm is far above the norm:
 coef is 1, torch multiplies every gradient by 1.0 (its cost is the same, the gradients stay), the guarded kernel multiplies by 1 as it always does.
-One guarded step is first compared with the restatement of tests/optim_guard_cases.py, exactly; the three kernels' own times come from the events."""
+One guarded step is first compared with the restatement of tests/optim_guard_cases.py, exactly; the three kernels' own times come from the events.
+With one of the option flags the extended step (k_adamx_step, k_adam_advance) gets a further pass of its own: one step with the options against
+the restatement of tests/optim_ext_cases.py, exactly, then the plain step twice (its spread), the step with the options, the extended kernel
+with no option set, torch's optimizer with the same options and the guarded step with the options; the ratios are reported, none is asserted."""
 import argparse
 import json
 import os
@@ -46,7 +49,7 @@ def parameter_set():
           (LRATE_MLP * 0.25, [basis])]
 
 
-def run(rounds, inner, dev='cuda:0'):
+def run(rounds, inner, dev='cuda:0', options=None):
   import numpy as np
   import torch
   import optim_cases as oc
@@ -174,6 +177,61 @@ def run(rounds, inner, dev='cuda:0'):
   assert sorted(gkern) == ['k_adam_step_guarded', 'k_grad_stats', 'k_grad_sumsq'] and all(c == rounds * inner for _, c in gkern.values()), gkern
   elements = sum(a.size for _, arrs in groups for a in arrs)
   tensors = sum(len(arrs) for _, arrs in groups)
+  extended = None
+  if options is not None:  # the extended step with the options of the command line, in a pass of its own
+    import optim_ext_cases as xc
+    okw = {k: v for k, v in options.items() if k != 'adamw'}
+    ours_cls, torch_cls = (optim.AdamW, torch.optim.AdamW) if options['adamw'] else (optim.AdamX, torch.optim.Adam)
+    lam, dec = okw.get('weight_decay', 1e-2 if options['adamw'] else 0.0), options['adamw']
+    ps, opt = make(ours_cls, **okw)
+    opt.step()
+    torch.cuda.synchronize()
+    for (lr, arrs), pg, gs in zip(groups, ps, host_grads):  # one step against the restatement, exactly
+      for a, p, g in zip(arrs, pg, gs):
+        n = a.size
+        a1, s21 = xc.pow_scalars(lr, 0.9, 0.999, np.ones(2))[:2] if okw.get('capturable') else oc.scalars(lr, 0.9, 0.999, 1)
+        wp, wm, wv, wx = xc.restate(a.reshape(-1), g.reshape(-1), np.zeros(n, np.float32), np.zeros(n, np.float32),
+                                    np.zeros(n, np.float32) if okw.get('amsgrad') else None, a1, s21, 0.9, 0.999, 1e-8, wd=0.0 if dec else lam,
+                                    decay=xc.decay_factor(lr, lam) if dec and lam else 1.0, maximize=bool(okw.get('maximize')))
+        oc.same(wp, p, 'extended p')
+        oc.same(wm, opt.state[p]['exp_avg'], 'extended m')
+        oc.same(wv, opt.state[p]['exp_avg_sq'], 'extended v')
+        if wx is not None:
+          oc.same(wx, opt.state[p]['max_exp_avg_sq'], 'extended vmax')
+    forced = make(optim.AdamX)[1]
+    forced.extended_kernel = True  # the extended kernel with no option set: what its record and its branches cost on their own
+    xlegs = [('hip_plain', legs[0][1].step), ('hip_options', opt.step), ('hip_plain_again', make(optim.Adam)[1].step),
+             ('hip_extended_kernel_no_options', forced.step), ('torch_options', make(torch_cls, **okw)[1].step),
+             ('hip_options_guarded', lambda o=make(ours_cls, **okw)[1]: o.step(max_grad_norm=1e30, skip_nonfinite=True))]
+    xtimes = {name: [] for name, _ in xlegs}
+    for r in range(rounds + 2):
+      for name, fn in xlegs:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(inner):
+          fn()
+        torch.cuda.synchronize()
+        if r >= 2:
+          xtimes[name].append((time.perf_counter() - t0) * 1e3 / inner)
+    xkern = {}
+    for tag, o in (('options', opt), ('no_options', forced)):
+      lib.dyn_profile_enable(1)
+      lib.dyn_profile_read(ms.ctypes.data, cnt.ctypes.data)
+      for _ in range(rounds * inner):
+        o.step()
+      torch.cuda.synchronize()
+      lib.dyn_profile_read(ms.ctypes.data, cnt.ctypes.data)
+      lib.dyn_profile_enable(0)
+      xkern[tag] = {lib.dyn_profile_name(i).decode(): round(float(ms[i]) / int(cnt[i]), 5) for i in range(nk) if cnt[i]}
+      assert 'k_adamx_step' in xkern[tag] and 'k_adam_step' not in xkern[tag], xkern
+    xmed = {name: statistics.median(v) for name, v in xtimes.items()}
+    per = 28 + (8 if okw.get('amsgrad') else 0)
+    q = lambda v: dict(median=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4))
+    extended = dict(options=options, step_ms={name: q(v) for name, v in xtimes.items()}, kernel_ms=xkern, bytes_per_element=per,
+                    plain_spread_ms=round(abs(xmed['hip_plain'] - xmed['hip_plain_again']), 4),
+                    options_over_plain=round(xmed['hip_options'] / min(xmed['hip_plain'], xmed['hip_plain_again']), 4),
+                    kernel_options_over_plain=round(xkern['options']['k_adamx_step'] / kernel_ms, 4),
+                    kernel_tb_per_s=round(per * elements / (xkern['options']['k_adamx_step'] * 1e-3) / 1e12, 3), exact=True)
   moved = 28 * elements
   q = lambda v: dict(median=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4))
   res = {name: q(v) for name, v in times.items()}
@@ -191,7 +249,7 @@ def run(rounds, inner, dev='cuda:0'):
               hip_minus_torch_default_ms=round(med['hip'] - min(med['torch_default'], med['torch_default_again']), 4),
               hip_no_slower_than_torch_default=bool(med['hip'] <= max(med['torch_default'], med['torch_default_again']) + spread),
               kernel_ms=round(kernel_ms, 5), kernel_bytes=moved, kernel_tb_per_s=round(moved / (kernel_ms * 1e-3) / 1e12, 3),
-              share_of_8_tb_per_s=round(moved / (kernel_ms * 1e-3) / 8e12, 3), exact=True, guard=guard, device=torch.cuda.get_device_name(0), torch=torch.__version__)
+              share_of_8_tb_per_s=round(moved / (kernel_ms * 1e-3) / 8e12, 3), exact=True, guard=guard, extended=extended, device=torch.cuda.get_device_name(0), torch=torch.__version__)
 
 
 def main():
@@ -199,8 +257,18 @@ def main():
   ap.add_argument('--rounds', type=int, default=30)
   ap.add_argument('--inner', type=int, default=20)
   ap.add_argument('--out', default=None)
+  ap.add_argument('--weight-decay', type=float, default=None, help='the extended step: coupled weight decay (decoupled with --adamw)')
+  ap.add_argument('--adamw', action='store_true', help='the extended step: optim.AdamW against torch.optim.AdamW (weight decay 1e-2 unless given)')
+  ap.add_argument('--amsgrad', action='store_true')
+  ap.add_argument('--maximize', action='store_true')
+  ap.add_argument('--capturable', action='store_true', help='step counts on the device (k_adam_advance follows the step)')
   a = ap.parse_args()
-  line = json.dumps(run(a.rounds, a.inner))
+  options = None
+  if a.weight_decay is not None or a.adamw or a.amsgrad or a.maximize or a.capturable:
+    options = dict(adamw=a.adamw, amsgrad=a.amsgrad, maximize=a.maximize, capturable=a.capturable)
+    if a.weight_decay is not None:
+      options['weight_decay'] = a.weight_decay
+  line = json.dumps(run(a.rounds, a.inner, options=options))
   print(line)
   if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
