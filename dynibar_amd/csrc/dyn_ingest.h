@@ -7,6 +7,8 @@
 //                      them with one dword store (bytes outside the row -- the padding of a pitched store, the neighbouring row -- are never
 //                      written: a partial chunk is stored bytewise).  The taps of neighbouring lanes overlap and are served by the caches:
 //                      the source is read from memory once.
+//   k_resize_area_f32  grid (cdiv(Wd * C, 256), Hd, B): one fp32 value per lane; the block sum, the decimation tables or, where an axis
+//                      enlarges, two taps per axis with area-mode coefficients.
 //   k_resize_linear_f32  grid (cdiv(Wd, 256), Hd, B): one fp32 value per lane, four taps.
 //   k_resize_nearest   the chunk scheme of the area kernel over pixels of PX bytes; with `below` the output is one byte per pixel.
 //   k_erode_disk_u8    grid (cdiv(W, 64), cdiv(H, 16), B): a 16 x 64 tile with its halo of r is staged in LDS (out-of-image = 1), then a row
@@ -87,6 +89,87 @@ __global__ __launch_bounds__(IG_THREADS) void k_resize_area_u8(IgAreaArgs a) {
     word |= (unsigned)(int)v << (8 * k);
   }
   ig_store_chunk(row + e0, word, lo, hi);
+}
+
+struct IgAreaF32Args {
+  const float* src;
+  float* dst;
+  long src_image, dst_pitch;  // bytes from one image to the next
+  int Hs, Ws, Hd, Wd, C;
+  int mode;                   // IG_AREA_BLOCK, IG_AREA_TABLE or IG_AREA_ENLARGE
+  int ix, iy;                 // the block of the integer-scale branch (1, 1: the copy)
+  const int *xcount, *xidx, *ycount, *yidx;
+  const float *xw, *yw;
+  int Kx, Ky;
+  double scale_x, scale_y, inv_x, inv_y;  // the enlarging branch: scale = 1 / inv, inv = (double)d / s
+};
+#define IG_AREA_BLOCK 0
+#define IG_AREA_TABLE 1
+#define IG_AREA_ENLARGE 2
+
+// the two-tap coefficient of INTER_AREA where an axis enlarges: source index and the weight of the second tap
+__device__ __forceinline__ void ig_area_tap(int d, double scale, double inv, int& s, float& f) {
+  s = (int)floor((double)d * scale);
+  f = (float)((double)(d + 1) - (double)(s + 1) * inv);
+  f = f <= 0.f ? 0.f : f - floorf(f);
+}
+
+// grid (cdiv(Wd * C, 256), Hd, B): one fp32 value per lane
+__global__ __launch_bounds__(IG_THREADS) void k_resize_area_f32(IgAreaF32Args a) {
+  const int e = blockIdx.x * IG_THREADS + threadIdx.x, y = blockIdx.y, C = a.C;
+  if (e >= a.Wd * C) return;
+  const int dx = e / C, c = e - dx * C;
+  const float* S = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(a.src) + (long)blockIdx.z * a.src_image);
+  float v;
+  if (a.mode == IG_AREA_BLOCK) {
+    const int area = a.ix * a.iy;
+    if (area == 1) {
+      v = S[((long)y * a.Ws + dx) * C + c];  // equal sizes: the copy
+    } else {
+      auto tap = [&](int k) {  // k = q * ix + p: row q, column p of the block
+        const int q = k / a.ix, p = k - q * a.ix;
+        return S[((long)ig_clamp(y * a.iy + q, a.Hs - 1) * a.Ws + ig_clamp(dx * a.ix + p, a.Ws - 1)) * C + c];
+      };
+      float sum = 0.f;
+      int k = 0;
+      for (; k <= area - 4; k += 4) sum = sum + (((tap(k) + tap(k + 1)) + tap(k + 2)) + tap(k + 3));
+      for (; k < area; ++k) sum = sum + tap(k);
+      v = sum * (1.f / (float)area);
+    }
+  } else if (a.mode == IG_AREA_TABLE) {
+    const int ny = ig_clamp(a.ycount[y], a.Ky), nx = ig_clamp(a.xcount[dx], a.Kx);
+    const int* xi = a.xidx + (long)dx * a.Kx;
+    const float* xw = a.xw + (long)dx * a.Kx;
+    v = 0.f;
+    for (int q = 0; q < ny; ++q) {
+      const float* srow = S + ((long)ig_clamp(a.yidx[(long)y * a.Ky + q], a.Hs - 1) * a.Ws) * C + c;
+      float rv = 0.f;
+      for (int p = 0; p < nx; ++p) rv = rv + srow[(long)ig_clamp(xi[p], a.Ws - 1) * C] * xw[p];
+      const float t = a.yw[(long)y * a.Ky + q] * rv;
+      v = q == 0 ? t : v + t;
+    }
+  } else {
+    int sx, sy;
+    float fx, fy;
+    ig_area_tap(dx, a.scale_x, a.inv_x, sx, fx);
+    ig_area_tap(y, a.scale_y, a.inv_y, sy, fy);
+    const bool edge = sx >= a.Ws - 1;
+    if (edge) sx = a.Ws - 1;
+    const float* r0 = S + ((long)ig_clamp(sy, a.Hs - 1) * a.Ws) * C + c;
+    const float* r1 = S + ((long)ig_clamp(sy + 1, a.Hs - 1) * a.Ws) * C + c;
+    float v0, v1;
+    if (edge) {
+      v0 = r0[(long)sx * C];
+      v1 = r1[(long)sx * C];
+    } else {
+      const float wx = 1.f - fx;
+      v0 = r0[(long)sx * C] * wx + r0[(long)(sx + 1) * C] * fx;
+      v1 = r1[(long)sx * C] * wx + r1[(long)(sx + 1) * C] * fx;
+    }
+    v = v0 * (1.f - fy) + v1 * fy;
+  }
+  float* row = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(a.dst) + (long)blockIdx.z * a.dst_pitch) + (long)y * a.Wd * C;
+  row[e] = v;
 }
 
 struct IgLinearArgs {
@@ -298,6 +381,41 @@ extern "C" int dyn_resize_area_u8(int B, int Hs, int Ws, int C, int Hd, int Wd, 
   if (C == 1) DYN_LAUNCH(DYN_K_RESIZE_AREA, who, k_resize_area_u8<1>, grid, dim3(IG_THREADS), 0, st, a);
   else if (C == 3) DYN_LAUNCH(DYN_K_RESIZE_AREA, who, k_resize_area_u8<3>, grid, dim3(IG_THREADS), 0, st, a);
   else DYN_LAUNCH(DYN_K_RESIZE_AREA, who, k_resize_area_u8<4>, grid, dim3(IG_THREADS), 0, st, a);
+  return 0;
+}
+
+extern "C" int dyn_resize_area_f32(int B, int Hs, int Ws, int C, int Hd, int Wd, const float* src, float* dst, int64_t dst_pitch,
+                                   const int32_t* xcount, const int32_t* xidx, const float* xw, int Kx, const int32_t* ycount, const int32_t* yidx,
+                                   const float* yw, int Ky, void* stream) {
+  const char* who = "dyn_resize_area_f32";
+  DYN_REQUIRE(C >= 1 && C <= 4, "%s: C=%d is unsupported (1..4)", who, C);
+  IG_REQUIRE_IMAGES(who, B, Hs, Ws, Hd, Wd, 4 * C);
+  DYN_REQUIRE(src && dst && vl_aligned(src, 4) && vl_aligned(dst, 4), "%s: src and dst are required, on 4 bytes", who);
+  DYN_REQUIRE(dst_pitch >= (int64_t)Hd * Wd * C * 4 && dst_pitch % 4 == 0, "%s: dst_pitch=%ld must be a multiple of 4 and at least %ld", who,
+              (long)dst_pitch, (long)Hd * Wd * C * 4);
+  IgAreaF32Args a;
+  a.src = src; a.dst = dst;
+  a.src_image = (long)Hs * Ws * C * 4;
+  a.dst_pitch = dst_pitch;
+  a.Hs = Hs; a.Ws = Ws; a.Hd = Hd; a.Wd = Wd; a.C = C;
+  a.scale_x = ig_scale(Ws, Wd); a.scale_y = ig_scale(Hs, Hd);
+  a.inv_x = (double)Wd / Ws; a.inv_y = (double)Hd / Hs;
+  a.ix = (int)a.scale_x; a.iy = (int)a.scale_y;
+  a.xcount = xcount; a.xidx = xidx; a.xw = xw; a.Kx = Kx;
+  a.ycount = ycount; a.yidx = yidx; a.yw = yw; a.Ky = Ky;
+  if (Hd > Hs || Wd > Ws) {
+    a.mode = IG_AREA_ENLARGE;
+  } else if (ig_integer_scale(a.scale_x) && ig_integer_scale(a.scale_y)) {
+    a.mode = IG_AREA_BLOCK;
+    DYN_REQUIRE((long)a.ix * Wd == Ws && (long)a.iy * Hd == Hs, "%s: integer scales %d, %d do not tile %d x %d", who, a.iy, a.ix, Hs, Ws);
+  } else {
+    a.mode = IG_AREA_TABLE;
+    DYN_REQUIRE(xcount && xidx && xw && ycount && yidx && yw && Kx >= 1 && Ky >= 1, "%s: the decimation tables of both axes are required", who);
+    DYN_REQUIRE(vl_aligned(xcount, 4) && vl_aligned(xidx, 4) && vl_aligned(xw, 4) && vl_aligned(ycount, 4) && vl_aligned(yidx, 4) && vl_aligned(yw, 4),
+                "%s: the tables must start on 4 bytes", who);
+  }
+  DYN_LAUNCH(DYN_K_RESIZE_AREA, who, k_resize_area_f32, dim3(dyn_cdiv((long)Wd * C, IG_THREADS), Hd, B), dim3(IG_THREADS), 0, (hipStream_t)stream,
+             a);
   return 0;
 }
 

@@ -381,6 +381,155 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_vv_finish(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The virtual views of many frames in one pass (dyn_vv_frames): batch entry b = f * V + v of the splat reads frame f = b / V, so no frame is
+// copied V times.  The arithmetic of every value is that of k_sobel_alpha, k_splat_project, k_splat_resolve<true> and k_vv_finish above,
+// operation for operation, and the sums run in the same ascending contribution id: the bytes equal the per-frame chain's.
+//
+//   k_vv_source    grid (cdiv(HW, 256), F): per frame pixel the splat's source (255 r, 255 g, 255 b, alpha) as one float4,
+//                  alpha = exp(-0.5 |sobel((1 / disp) / 10)|) with the nine taps recomputed from disp (replicate border)
+//   k_vv_project   k_splat_project with depth = 1 / disp[f] and the intrinsics of frame f
+//   k_vv_resolve   grid (cdiv(HW, 256), B): the four channels the epilogue reads (the splatted importance and ones channels feed nothing) and
+//                  the first half of the epilogue: one dword per view pixel, bytes 0..2 = uint8(255 clip(rgb / 255, 0, 1)), byte 3 = alpha > 0.5
+//   k_vv_erode     the disk(1) erosion of byte 3 (out-of-image neighbours do not erode) and the masked rgb bytes: the values are in 0..1
+//                  and the mask is 0 or 1, so clip(v * m, 0, 1) is v or 0 and the byte is the resolved one or 0
+// ---------------------------------------------------------------------------------------------------------------------------------
+// (1 / disp) / 10 as torch forms it for a tensor on the device it runs on: a HIP tensor over a host scalar is multiplied by the fp32
+// reciprocal of the scalar, a host tensor is divided
+__device__ __forceinline__ float vv_tenth(float depth, int by_division) { return by_division ? depth / 10.f : depth * (1.f / 10.f); }
+
+__global__ __launch_bounds__(SPLAT_THREADS) void k_vv_source(const float* __restrict__ img, const float* __restrict__ disp, int H, int W,
+                                                             int by_division, float4* __restrict__ rgba) {
+  const long HW = (long)H * W;
+  const long p = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x;
+  if (p >= HW) return;
+  const long f = blockIdx.y;
+  const int y = (int)(p / W), xx = (int)(p - (long)y * W);
+  const float* d = disp + f * HW;
+  const int ym = y > 0 ? y - 1 : 0, yp = y < H - 1 ? y + 1 : H - 1;
+  const int xm = xx > 0 ? xx - 1 : 0, xp = xx < W - 1 ? xx + 1 : W - 1;
+  auto v = [&](int yy, int x2) { return vv_tenth(1.f / d[(long)yy * W + x2], by_division); };
+  const float gx = ((v(ym, xp) - v(ym, xm)) + 2.f * (v(y, xp) - v(y, xm))) + (v(yp, xp) - v(yp, xm));
+  const float gy = ((v(yp, xm) - v(ym, xm)) + 2.f * (v(yp, xx) - v(ym, xx))) + (v(yp, xp) - v(ym, xp));
+  const float* c = img + (f * HW + p) * 3;
+  float4 o;
+  o.x = c[0] * 255.f;
+  o.y = c[1] * 255.f;
+  o.z = c[2] * 255.f;
+  o.w = expf(-0.5f * sqrtf(gx * gx + gy * gy));
+  rgba[f * HW + p] = o;
+}
+
+// grid (<= SPLAT_PROJECT_BLOCKS, B): as k_splat_project
+__global__ __launch_bounds__(SPLAT_THREADS) void k_vv_project(const float* __restrict__ disp, const float* __restrict__ kinv,
+                                                              const float* __restrict__ rot, const float* __restrict__ kdst,
+                                                              const float* __restrict__ tr, int H, int W, int V, float* __restrict__ flow,
+                                                              float* __restrict__ imp, unsigned* __restrict__ minmax) {
+  const int b = blockIdx.y, f = b / V;
+  const long HW = (long)H * W;
+  const float* Ki = kinv + f * 9;
+  const float* Rm = rot + b * 9;
+  const float* Kd = kdst + f * 9;
+  const float* tv = tr + b * 3;
+  float hi = -INFINITY, nlo = -INFINITY;
+  for (long p = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x; p < HW; p += (long)gridDim.x * SPLAT_THREADS) {
+    const int y = (int)(p / W), x = (int)(p - (long)y * W);
+    const float xf = (float)x, yf = (float)y, d = 1.f / disp[f * HW + p];
+    float P[3], S[3], Q[3];
+    for (int i = 0; i < 3; ++i) P[i] = ((d * Ki[i * 3]) * xf + (d * Ki[i * 3 + 1]) * yf) + (d * Ki[i * 3 + 2]);
+    for (int i = 0; i < 3; ++i) S[i] = ((Rm[i * 3] * P[0] + Rm[i * 3 + 1] * P[1]) + Rm[i * 3 + 2] * P[2]) + tv[i];
+    for (int i = 0; i < 3; ++i) Q[i] = (Kd[i * 3] * S[0] + Kd[i * 3 + 1] * S[1]) + Kd[i * 3 + 2] * S[2];
+    const float zc = Q[2] < 1e-8f ? 1e-8f : Q[2];
+    flow[(b * 2) * HW + p] = Q[0] / zc - xf;
+    flow[(b * 2 + 1) * HW + p] = Q[1] / zc - yf;
+    const float im = 1.f / Q[2];
+    imp[b * HW + p] = im;
+    hi = fmaxf(hi, im);
+    nlo = fmaxf(nlo, -im);
+  }
+  hi = wave_max(hi);
+  nlo = wave_max(nlo);
+  float* red = reinterpret_cast<float*>(dyn_smem);  // [2][waves]
+  constexpr int NW = SPLAT_THREADS / DYN_WAVE;
+  if (dyn_lane() == 0) {
+    red[dyn_wave()] = hi;
+    red[NW + dyn_wave()] = nlo;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < NW; ++w) {
+      hi = fmaxf(hi, red[w]);
+      nlo = fmaxf(nlo, red[NW + w]);
+    }
+    atomicMax(&minmax[2 * b], splat_ord(hi));
+    atomicMax(&minmax[2 * b + 1], splat_ord(nlo));
+  }
+}
+
+struct VvResolveArgs {
+  int H, W, V;
+  const float4* rgba;   // [F,H,W] (r, g, b, alpha)
+  const float* flow;    // [B,2,H,W]
+  const float* mult;    // [B,H,W]
+  float eps;
+  const unsigned* ids;
+  const int* start;
+  const int* end;
+  unsigned* pix;        // [B,H,W]
+};
+
+__device__ __forceinline__ unsigned vv_byte(float feat) {
+  float v = fminf(fmaxf(feat / 255.f, 0.f), 1.f);
+  v = 255.f * fminf(fmaxf(v * 1.f, 0.f), 1.f);
+  return (unsigned)(int)v;
+}
+
+__global__ __launch_bounds__(SPLAT_THREADS) void k_vv_resolve(VvResolveArgs a) {
+  const int b = blockIdx.y;
+  const long HW = (long)a.H * a.W;
+  const long p = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x;
+  if (p >= HW) return;
+  const long i = b * HW + p;
+  const float4* frame = a.rgba + (long)(b / a.V) * HW;
+  float n0 = 0.f, n1 = 0.f, n2 = 0.f, n3 = 0.f, den = 0.f;
+  const int s = a.start[i], e = a.end[i];
+  for (int k = s; k < e; ++k) {
+    const unsigned id = a.ids[k];
+    const long src = (long)(id >> 2);
+    const long sp = src - b * HW;
+    const int sy = (int)(sp / a.W), sx = (int)(sp - (long)sy * a.W);
+    const SplatTap t = splat_tap(sx, sy, a.flow[(b * 2) * HW + sp], a.flow[(b * 2 + 1) * HW + sp], a.H, a.W);
+    const float w = splat_corner_weight(t, (int)(id & 3u));
+    const float m = a.mult[src];
+    const float4 f = frame[sp];
+    n0 += w * (f.x * m);
+    n1 += w * (f.y * m);
+    n2 += w * (f.z * m);
+    n3 += w * (f.w * m);
+    den += w * m;
+  }
+  const float d = den + a.eps;
+  a.pix[i] = vv_byte(n0 / d) | (vv_byte(n1 / d) << 8) | (vv_byte(n2 / d) << 16) | ((n3 / d > 0.5f ? 1u : 0u) << 24);
+}
+
+// n = B * H * W view pixels; view b goes to out + b * pitch
+__global__ __launch_bounds__(SPLAT_THREADS) void k_vv_erode(const unsigned* __restrict__ pix, long n, int H, int W, long pitch,
+                                                            unsigned char* __restrict__ out) {
+  const long i = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const long HW = (long)H * W;
+  const long b = i / HW, p = i - b * HW;
+  const int y = (int)(p / W), x = (int)(p - (long)y * W);
+  const unsigned v = pix[i];
+  bool m = (v >> 24) != 0u;
+  if (y > 0) m = m && (pix[i - W] >> 24) != 0u;
+  if (y < H - 1) m = m && (pix[i + W] >> 24) != 0u;
+  if (x > 0) m = m && (pix[i - 1] >> 24) != 0u;
+  if (x < W - 1) m = m && (pix[i + 1] >> 24) != 0u;
+  unsigned char* o = out + b * pitch + p * 3;
+  for (int c = 0; c < 3; ++c) o[c] = m ? (unsigned char)(v >> (8 * c)) : (unsigned char)0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------
 static inline size_t splat_align(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -531,5 +680,85 @@ extern "C" int dyn_vv_finish(const float* feat, int B, int C, int H, int W, uint
   const long n = (long)B * H * W;
   DYN_LAUNCH(DYN_K_VV_FINISH, "k_vv_finish", k_vv_finish, dim3(dyn_cdiv(n, SPLAT_THREADS)), dim3(SPLAT_THREADS), 0, (hipStream_t)stream, feat,
              n, C, H, W, (unsigned char*)out);
+  return 0;
+}
+
+// ---- dyn_vv_frames ---------------------------------------------------------------------------------------------------------------------
+// Frames go through the splat in groups: a group is as many frames as sort in the number of 8-bit passes one frame's views need (the key of
+// a group of G frames has bits(G * V * H * W) bits: at 8 x 288 x 512 one frame takes 3 passes, 13 frames still 3, 16 frames 4).
+#define VV_MAX_VIEWS 65535  // views per group: blockIdx.y
+struct VvLayout {
+  int G;            // frames per group
+  SplatLayout L;    // of a full group
+  size_t rgba, total;
+};
+static bool vv_layout(int F, int V, int H, int W, VvLayout& Y) {
+  if (F <= 0 || V <= 0 || V > VV_MAX_VIEWS || H <= 0 || W <= 0) return false;
+  if ((long)F * V > (1L << 28) / ((long)H * W)) return false;  // F * V * H * W <= 2^28, without overflow
+  SplatLayout one;
+  if (!splat_layout(V, H, W, one)) return false;
+  const long per = (long)V * H * W;
+  long g = ((1L << (8 * one.passes)) - 1) / per;  // the sentinel g * per stays below 2^(8 passes)
+  if (g > VV_MAX_VIEWS / V) g = VV_MAX_VIEWS / V;  // a view is a row of the grid
+  Y.G = (int)(g < 1 ? 1 : (g > F ? F : g));
+  if (!splat_layout(Y.G * V, H, W, Y.L)) return false;
+  Y.rgba = Y.L.total;
+  Y.total = Y.rgba + splat_align((size_t)Y.G * H * W * sizeof(float4));
+  return true;
+}
+
+extern "C" size_t dyn_vv_frames_workspace_bytes(int F, int V, int H, int W) {
+  VvLayout Y;
+  return vv_layout(F, V, H, W, Y) ? Y.total : 0;
+}
+
+extern "C" int dyn_vv_frames(const DynVvFramesParams* p, void* stream) {
+  const char* who = "dyn_vv_frames";
+  DYN_REQUIRE(p, "%s: null params", who);
+  VvLayout Y;
+  DYN_REQUIRE(vv_layout(p->F, p->V, p->H, p->W, Y), "%s: bad shape F=%d V=%d H=%d W=%d (sizes >= 1, V <= 65535, F*V*H*W <= 2^28)", who, p->F, p->V, p->H, p->W);
+  DYN_REQUIRE(p->img && p->disp && p->k && p->k_inv && p->rot && p->t && p->out, "%s: img, disp, k, k_inv, rot, t and out are required", who);
+  DYN_REQUIRE(p->out_pitch >= (int64_t)p->H * p->W * 3, "%s: out_pitch=%ld is smaller than a view of %ld bytes", who, (long)p->out_pitch,
+              (long)p->H * p->W * 3);
+  DYN_REQUIRE(p->workspace && p->workspace_bytes >= Y.total && ((uintptr_t)p->workspace & 15) == 0,
+              "%s: workspace of %zu bytes given, %zu needed, on 16 bytes", who, p->workspace_bytes, Y.total);
+  DYN_REQUIRE(p->eps == p->eps, "%s: eps is NaN", who);
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)p->workspace;
+  const long HW = (long)p->H * p->W;
+  const int V = p->V, hwblocks = dyn_cdiv(HW, SPLAT_THREADS);
+  const int pblocks = hwblocks < SPLAT_PROJECT_BLOCKS ? hwblocks : SPLAT_PROJECT_BLOCKS;
+  float4* rgba = (float4*)(ws + Y.rgba);
+  for (int f0 = 0; f0 < p->F; f0 += Y.G) {
+    const int G = p->F - f0 < Y.G ? p->F - f0 : Y.G, B = G * V;
+    SplatLayout L;
+    DYN_REQUIRE(splat_layout(B, p->H, p->W, L) && L.total <= Y.L.total, "%s: internal: the layout of %d views does not fit", who, B);
+    const float* disp = p->disp + (long)f0 * HW;
+    float* flow = (float*)(ws + L.flow);
+    float* imp = (float*)(ws + L.imp);
+    float* mult = (float*)(ws + L.mult);
+    unsigned* minmax = (unsigned*)(ws + L.minmax);
+    if (hipMemsetAsync(minmax, 0, (size_t)B * 2 * 4, st) != hipSuccess) {
+      dyn_set_error("%s: hipMemsetAsync failed", who);
+      return DYN_E_LAUNCH;
+    }
+    DYN_LAUNCH(DYN_K_SOBEL_ALPHA, "k_vv_source", k_vv_source, dim3(hwblocks, G), dim3(SPLAT_THREADS), 0, st, p->img + (long)f0 * HW * 3, disp, p->H,
+               p->W, p->tenth_by_division ? 1 : 0, rgba);
+    DYN_LAUNCH(DYN_K_SPLAT_PROJECT, "k_vv_project", k_vv_project, dim3(pblocks, B), dim3(SPLAT_THREADS), 2 * (SPLAT_THREADS / DYN_WAVE) * 4, st,
+               disp, p->k_inv + (long)f0 * 9, p->rot + (long)f0 * V * 9, p->k + (long)f0 * 9, p->t + (long)f0 * V * 3, p->H, p->W, V, flow, imp, minmax);
+    DYN_LAUNCH(DYN_K_SPLAT_KEYS, "k_splat_keys", k_splat_keys, dim3(hwblocks, B), dim3(SPLAT_THREADS), 0, st, (const float*)flow, p->H, p->W,
+               (unsigned)L.N, (const float*)imp, (const unsigned*)minmax, mult, (unsigned*)(ws + L.keys0), (int*)(ws + L.start), (int*)(ws + L.end));
+    unsigned* ids = nullptr;
+    int rc = splat_sort(L, ws, &ids, st);
+    if (rc) return rc;
+    VvResolveArgs a;
+    a.H = p->H; a.W = p->W; a.V = V;
+    a.rgba = rgba; a.flow = flow; a.mult = mult; a.eps = p->eps;
+    a.ids = ids; a.start = (const int*)(ws + L.start); a.end = (const int*)(ws + L.end);
+    a.pix = (unsigned*)imp;  // the importance was consumed by k_splat_keys: its plane holds the resolved pixels
+    DYN_LAUNCH(DYN_K_SPLAT_RESOLVE, "k_vv_resolve", k_vv_resolve, dim3(hwblocks, B), dim3(SPLAT_THREADS), 0, st, a);
+    DYN_LAUNCH(DYN_K_VV_FINISH, "k_vv_erode", k_vv_erode, dim3(dyn_cdiv(L.N, SPLAT_THREADS)), dim3(SPLAT_THREADS), 0, st, (const unsigned*)a.pix,
+               L.N, p->H, p->W, (long)p->out_pitch, p->out + (long)f0 * V * p->out_pitch);
+  }
   return 0;
 }

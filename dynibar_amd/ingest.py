@@ -9,6 +9,9 @@
     monocular.py:173-181, :204 (the static mask)               ->   ingest.static_mask(raw_u8, (w, h))
     save_monocular_cameras.py:72, :93-95 and monocular.py:162  ->   ingest.disparity(depth, (w, h), scale)
     python save_monocular_cameras.py --data_dir D --cvd_dir C  ->   python -m dynibar_amd.ingest --data_dir D --cvd_dir C
+    cv2.resize(img_1, (w, h), interpolation=cv2.INTER_AREA)    ->   ingest.resize_area_f32(img_1, (w, h))  (float32: shrinking and enlarging)
+    render_source_vv.py:253-330 for every frame of a scene     ->   ingest.build_virtual_views(img_1, depth, K_t, cam_c2w, (w, h))
+    python render_source_vv.py --data_dir D --cvd_dir C        ->   python -m dynibar_amd.ingest --data_dir D --cvd_dir C --virtual_views
 
 ``size`` is ``(width, height)``, the order of cv2's ``dsize``.  The path from decoded files to a resident scene needs numpy, PIL and this
 package only: ``prepare_monocular`` runs the loader's chains for every frame of a scene and ``DeviceScene.from_decoded`` hands the result to
@@ -205,7 +208,8 @@ def _device_table(s, d, device):
 # ---- the five operations -------------------------------------------------------------------------------------------------------------
 def resize_area(images, size, out=None, device=None):
   """``cv2.resize(images, size, interpolation=cv2.INTER_AREA)`` for shrinking: uint8 ``[H, W]``, ``[H, W, C]`` or ``[B, H, W, C]`` with C in
-  1, 3, 4 -> uint8 of the same form at ``size = (width, height)``.  ``out``: a uint8 tensor to write into; its images may be spaced apart."""
+  1, 3, 4 -> uint8 of the same form at ``size = (width, height)``.  ``out``: a uint8 tensor to write into; its images may be spaced apart.
+  (float32 images, shrinking or enlarging: ``resize_area_f32``.)"""
   dev = _device(device, images, out)
   t4, back = _batched(_tensor(images, 'images', (torch.uint8,), dev), 'images', _IMAGE_LAYOUTS)
   B, Hs, Ws, C = (int(v) for v in t4.shape)
@@ -225,6 +229,34 @@ def resize_area(images, size, out=None, device=None):
     tx, ty = _device_table(Ws, Wd, dev), _device_table(Hs, Hd, dev)
     Kx, Ky = int(tx[1].shape[1]), int(ty[1].shape[1])
   call('dyn_resize_area_u8', B, Hs, Ws, C, Hd, Wd, _p(t4), _p(o), pitch, _p(tx[0]), _p(tx[1]), _p(tx[2]), Kx, _p(ty[0]), _p(ty[1]), _p(ty[2]), Ky,
+       stream_of(t4))
+  return out if out is not None else back(o)
+
+
+def resize_area_f32(images, size, out=None, device=None):
+  """``cv2.resize(images, size, interpolation=cv2.INTER_AREA)`` on float32, shrinking or enlarging: ``[H, W]``, ``[H, W, C]`` or ``[B, H, W, C]``
+  with C in 1..4 -> float32 of the same form at ``size = (width, height)``.  Where an axis enlarges OpenCV's INTER_AREA is its two-tap linear
+  kernel with area-mode coefficients, on both axes.  The source must be contiguous.  ``out``: a float32 tensor to write into; its images may
+  be spaced apart.  (``resize_area`` stays the uint8 form and keeps refusing everything else.)"""
+  dev = _device(device, images, out)
+  if isinstance(images, torch.Tensor) and not images.is_contiguous():
+    raise ValueError(f'images must be contiguous, got strides {list(images.stride())} for {list(images.shape)}')
+  if isinstance(images, np.ndarray) and not images.flags.c_contiguous:
+    raise ValueError(f'images must be contiguous, got strides {list(images.strides)} for {list(images.shape)}')
+  t4, back = _batched(_tensor(images, 'images', (torch.float32,), dev), 'images', _IMAGE_LAYOUTS)
+  B, Hs, Ws, C = (int(v) for v in t4.shape)
+  Wd, Hd = _size(size)
+  if not 1 <= C <= 4:
+    raise ValueError(f'float32 images must have 1 to 4 channels, got {C}')
+  if Hs * Ws * C * 4 >= 2 ** 31 or Hd * Wd * C * 4 >= 2 ** 31 or Hd > 65535 or B > 65535:
+    raise ValueError(f'{B} images of {Hs} x {Ws} x {C} -> {Hd} x {Wd} are too large (H*W*C*4 < 2^31, at most 65535 rows and images per call)')
+  o, pitch = _out(None if out is None else _batched(out, 'out', _IMAGE_LAYOUTS)[0], (B, Hd, Wd, C), torch.float32, dev, 'resize_area_f32')
+  tx = ty = (None, None, None)
+  Kx = Ky = 0
+  if Hd <= Hs and Wd <= Ws and not (is_integer_scale(axis_scale(Ws, Wd)) and is_integer_scale(axis_scale(Hs, Hd))):
+    tx, ty = _device_table(Ws, Wd, dev), _device_table(Hs, Hd, dev)
+    Kx, Ky = int(tx[1].shape[1]), int(ty[1].shape[1])
+  call('dyn_resize_area_f32', B, Hs, Ws, C, Hd, Wd, _p(t4), _p(o), pitch, _p(tx[0]), _p(tx[1]), _p(tx[2]), Kx, _p(ty[0]), _p(ty[1]), _p(ty[2]), Ky,
        stream_of(t4))
   return out if out is not None else back(o)
 
@@ -442,6 +474,145 @@ def prepare_monocular(frames, depth, dynamic_masks, static_masks, flows, flow_ma
               source_masks=None if source_masks is None else up(source_masks))
 
 
+# ---- virtual source views (render_source_vv.py:253-330) for every frame of a scene ------------------------------------------------------
+_VV_WORKSPACE = {}    # (device, stream) -> the scratch of dyn_vv_frames, grown on demand
+
+
+def _vv_workspace(F, V, H, W, dev):
+  need = int(_lib.lib().dyn_vv_frames_workspace_bytes(F, V, H, W))
+  if need == 0:
+    raise ValueError(f'virtual views of {F} frames x {V} views of {H} x {W} are unsupported (sizes >= 1, V <= 65535, frames*views*H*W <= 2^28 per '
+                     f'batch: lower batch)')
+  key = (str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else 0)
+  ws = _VV_WORKSPACE.get(key)
+  if ws is None or ws.numel() < need:
+    ws = _VV_WORKSPACE[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+  return ws
+
+
+def _upload(a, dev):
+  """a small host float array -> float32 on ``dev`` without a synchronisation (through pinned memory, as the tables)"""
+  t = torch.from_numpy(np.ascontiguousarray(a)).float().contiguous()
+  return t.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else t
+
+
+def relative_transforms(c2w, vv_c2w):
+  """``inv([vv_c2w; 0 0 0 1]) @ c2w`` for every frame and view in float64 on the host, as ``virtual_views.frame_batch`` forms them
+  (render_source_vv.py:297-305): c2w ``[N, 4, 4]``, vv_c2w ``[N, V, 3, 4]`` -> (rot float64 ``[N, V, 3, 3]``, t float64 ``[N, V, 3]``)."""
+  N, V = len(vv_c2w), len(vv_c2w[0])
+  rot, tr = np.empty((N, V, 3, 3)), np.empty((N, V, 3))
+  for i in range(N):
+    ref = np.asarray(c2w[i], dtype=np.float64)
+    for k in range(V):
+      tgt = np.eye(4)
+      tgt[:3, :4] = vv_c2w[i][k]
+      T = np.dot(np.linalg.inv(tgt), ref)
+      rot[i, k], tr[i, k] = T[:3, :3], T[:3, 3]
+  return rot, tr
+
+
+def virtual_views(images01, disp, K, c2w, vv_c2w, out=None, batch=DEFAULT_BATCH, device=None):
+  """The virtual source views of N frames, ``batch`` frames x V views per ``dyn_vv_frames`` call: what
+  ``np.stack([virtual_views.render_frame_virtual_views(images01[i], disp[i], K[i], c2w[i], vv_c2w[i]) for i in range(N)])`` returns, bit for
+  bit, on the device and from one copy of each frame.
+
+  images01  float32 ``[N, H, W, 3]`` in 0..1 and  disp  float32 ``[N, H, W]``, at the working size
+  K         ``[3, 3]`` or ``[N, 3, 3]``: source = destination intrinsics;  c2w ``[N, 4, 4]``;  vv_c2w ``[N, V, 3, 4]`` (host arrays)
+  out       None, or uint8 ``[N, V, H, W, 3]`` on the device with contiguous views at a uniform spacing (``stride(0) == V * stride(1)``)
+  -> uint8 ``[N, V, H, W, 3]`` on the device.  The poses are combined on the host in float64 and K is inverted by torch on the host, both as
+  the per-frame path does; nothing synchronises."""
+  dev = _device(device, images01, disp, out)
+  img = _tensor(images01, 'images01', (torch.float32,), dev)
+  dsp = _tensor(disp, 'disp', (torch.float32,), dev)
+  if img.dim() != 4 or img.shape[3] != 3 or min(img.shape) < 1:
+    raise ValueError(f'images01 must be float32 [N, H, W, 3], got {list(img.shape)}')
+  N, H, W, _ = (int(v) for v in img.shape)
+  if tuple(dsp.shape) != (N, H, W):
+    raise ValueError(f'disp must be float32 {[N, H, W]}, got {list(dsp.shape)}')
+  vv = np.asarray(vv_c2w, dtype=np.float64)
+  cam = np.asarray(c2w, dtype=np.float64)
+  if vv.ndim != 4 or vv.shape[0] != N or vv.shape[1] < 1 or vv.shape[2:] != (3, 4) or cam.shape != (N, 4, 4):
+    raise ValueError(f'c2w must be [{N}, 4, 4] and vv_c2w [{N}, V, 3, 4], got {list(cam.shape)} and {list(vv.shape)}')
+  V = int(vv.shape[1])
+  k = torch.from_numpy(np.array(K)).float()
+  if k.dim() == 2:
+    k = k[None].expand(N, 3, 3)
+  if tuple(k.shape) != (N, 3, 3):
+    raise ValueError(f'K must be [3, 3] or [{N}, 3, 3], got {list(k.shape)}')
+  batch = int(batch)
+  if batch < 1:
+    raise ValueError(f'batch={batch}')
+  k = k.contiguous()
+  rot, tr = relative_transforms(cam, vv)
+  kd, kinv, rd, td = (_upload(x, dev) for x in (k.numpy(), k.inverse().numpy(), rot.reshape(N * V, 3, 3), tr.reshape(N * V, 3)))
+  if out is None:
+    out = torch.empty((N, V, H, W, 3), dtype=torch.uint8, device=dev)
+  else:
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (N, V, H, W, 3):
+      raise ValueError(f'virtual_views: out must be a uint8 tensor {[N, V, H, W, 3]} on {dev}')
+    if not out[0, 0].is_contiguous() or (V > 1 and out.stride(1) < H * W * 3) or (N > 1 and out.stride(0) != V * out.stride(1)):
+      raise ValueError('virtual_views: the views of out must be contiguous and evenly spaced (stride(0) == V * stride(1))')
+  pitch = int(out.stride(1)) if V > 1 else (int(out.stride(0)) if N > 1 else H * W * 3)
+  F = min(batch, N)
+  ws = _vv_workspace(F, V, H, W, dev)
+  for i in range(0, N, F):
+    j = min(N, i + F)
+    p = _lib.params('DynVvFramesParams', F=j - i, V=V, H=H, W=W, img=_p(img[i:j]), disp=_p(dsp[i:j]), k=_p(kd[i:j]), k_inv=_p(kinv[i:j]),
+                    rot=_p(rd[i * V:j * V]), t=_p(td[i * V:j * V]), eps=1e-7, tenth_by_division=0 if dev.type == 'cuda' else 1, out=_p(out[i:j]),
+                    out_pitch=pitch, workspace=_p(ws), workspace_bytes=int(ws.numel()))
+    call('dyn_vv_frames', p, stream_of(img))
+  return out
+
+
+def build_virtual_views(net_images, depth, intrinsics_t, cam_c2w, size, batch=DEFAULT_BATCH, device=None, out=None):
+  """render_source_vv.py from the decoded ``--cvd_dir`` records of a scene, with cv2-style resizes, on the device.
+
+  net_images    float32 ``[N, h, w, 3]``: ``img_1`` of every record, channels last
+  depth         float32 ``[N, h, w]``: ``depth[0, 0]`` of every record
+  intrinsics_t  the stored transposed ``K`` of the records, ``[3, 3]`` or ``[N, 3, 3]``, for the ``w x h`` network image
+  cam_c2w       ``[N, 4, 4]``;  size = ``(final_w, final_h)``
+  -> (views uint8 ``[N, 8, H, W, 3]`` on the device, source_vv_poses float32 ``[8, 3, 4, N]`` on the host: the array the script saves).
+  The 5th depth percentiles come from ``depth_bounds`` (one copy of N floats to the host, which the float64 pose algebra needs); the frame is
+  resized with ``resize_area_f32``, ``1 / depth`` with ``resize_linear`` (reciprocal first, as the script has it)."""
+  from . import virtual_views as vvmod
+  dev = _device(device, net_images, depth, out)
+  img = _tensor(net_images, 'net_images', (torch.float32,), dev)
+  dep = _tensor(depth, 'depth', (torch.float32,), dev)
+  if img.dim() != 4 or img.shape[3] != 3 or dep.dim() != 3 or dep.shape[0] != img.shape[0] or min(img.shape) < 1 or min(dep.shape) < 1:
+    raise ValueError(f'net_images must be float32 [N, h, w, 3] and depth [N, h, w], got {list(img.shape)} and {list(dep.shape)}')
+  N, net_h, net_w, _ = (int(v) for v in img.shape)
+  W, H = _size(size)
+  Kt = np.asarray(intrinsics_t)
+  Kt = np.broadcast_to(Kt, (N, 3, 3)) if Kt.ndim == 2 else Kt
+  cams = [np.asarray(c) for c in cam_c2w]
+  if Kt.shape != (N, 3, 3) or len(cams) != N or any(c.shape != (4, 4) for c in cams):
+    raise ValueError(f'intrinsics_t must be [3, 3] or [{N}, 3, 3] and cam_c2w [{N}, 4, 4]')
+  Ks = [scaled_intrinsics(Kt[i], W, H, net_w, net_h) for i in range(N)]
+  fifth = depth_bounds(dep, device=dev)[:, 0].cpu().numpy()
+  fx, fy = Ks[-1][0, 0], Ks[-1][1, 1]  # (the last frame's intrinsics, as in the reference)
+  hwf = np.array([H, W, (fx + fy) / 2.0]).reshape([3, 1])
+  vv_poses_final, vsv = vvmod.virtual_view_poses(cams, list(fifth), hwf)
+  poses = np.moveaxis(vv_poses_final, 0, -1).astype(np.float32)
+  V = int(vsv.shape[1])
+  if out is None:
+    out = torch.empty((N, V, H, W, 3), dtype=torch.uint8, device=dev)
+  batch = int(batch)
+  if batch < 1:
+    raise ValueError(f'batch={batch}')
+  for i in range(0, N, batch):
+    j = min(N, i + batch)
+    small = resize_area_f32(img[i:j], (W, H), device=dev)
+    disp = resize_linear_reciprocal(dep[i:j], (W, H), device=dev)
+    virtual_views(small, disp, np.stack(Ks[i:j]), np.stack(cams[i:j]), vsv[i:j], out=out[i:j], batch=batch, device=dev)
+  return out, poses
+
+
+def resize_linear_reciprocal(depth, size, out=None, device=None):
+  """``cv2.resize(1.0 / depth, size, interpolation=cv2.INTER_LINEAR)``: the reciprocal in float32 first, then the resize
+  (save_monocular_cameras.py:72, :93-95 and render_source_vv.py:266, :279).  float32 ``[H, W]`` or ``[B, H, W]``."""
+  return _linear(depth, size, out, device, True, None, 'resize_linear_reciprocal')
+
+
 # ---- the command-line tool: python -m dynibar_amd.ingest ------------------------------------------------------------------------------
 def poses_bounds(c2w_mats, bounds, h, w, fx, fy):
   """The rows of ``poses_bounds_cvd.npy``, the file ``load_mono_data`` reads: ``c2w_mats`` ``[N, 4, 4]`` (or ``[N, 3, 4]``), ``bounds`` ``[N, 2]`` ->
@@ -512,6 +683,8 @@ def main(argv=None):
   ap.add_argument('--data_dir', required=True, help='the scene: frames are read from <data_dir>/dense/images, results go under <data_dir>/dense')
   ap.add_argument('--cvd_dir', required=True, help='the folder with the consistent-depth results, one .npz per frame')
   ap.add_argument('--batch', type=int, default=DEFAULT_BATCH, help='frames per kernel launch')
+  ap.add_argument('--virtual_views', action='store_true',
+                  help='also write source_virtual_views_WxH/NNNNN/KK.png and source_vv_poses.npy (render_source_vv.py) with cv2-style resizes')
   a = ap.parse_args(argv)
   records = sorted(glob.glob(os.path.join(a.cvd_dir, '*.npz')))
   if not records:
@@ -542,7 +715,36 @@ def main(argv=None):
       Image.fromarray(small[k]).save(os.path.join(frame_out, f'{start + k:05d}.png'))
       np.save(os.path.join(disp_out, f'{start + k:05d}.npy'), disp[k])
   np.save(os.path.join(dense, 'poses_bounds_cvd.npy'), poses_bounds(cams, bounds, out_h, out_w, K[0, 0], K[1, 1]))
+  if a.virtual_views:
+    write_virtual_views(records, dense, (out_w, out_h), a.batch, dev)
   return 0
+
+
+def write_virtual_views(records, dense, size, batch=DEFAULT_BATCH, device=None):
+  """The files of render_source_vv.py from the ``*.npz`` depth records, under ``dense``: ``source_virtual_views_WxH/NNNNN/KK.png`` and
+  ``source_vv_poses.npy`` -> the list of the PNG paths, in the order ``virtual_views.main`` reports them."""
+  import os
+
+  from PIL import Image
+  net, depth, Kt, cams = [], [], [], []
+  for path in records:
+    with np.load(path) as z:
+      net.append(np.ascontiguousarray(z['img_1'][0].transpose(1, 2, 0), dtype=np.float32))
+      depth.append(np.ascontiguousarray(z['depth'][0, 0], dtype=np.float32))
+      Kt.append(z['K'][0, 0, 0])
+      cams.append(z['cam_c2w'][0])
+  views, poses = build_virtual_views(np.stack(net), np.stack(depth), np.stack(Kt), cams, size, batch=batch, device=device)
+  np.save(os.path.join(dense, 'source_vv_poses.npy'), poses)
+  save_dir = os.path.join(dense, 'source_virtual_views_%dx%d' % size)
+  written = []
+  for i in range(len(records)):
+    sub = os.path.join(save_dir, '%05d' % i)
+    os.makedirs(sub, exist_ok=True)
+    frame = views[i].cpu().numpy()
+    for k in range(frame.shape[0]):
+      written.append(os.path.join(sub, '%02d.png' % k))
+      Image.fromarray(frame[k]).save(written[-1])
+  return written
 
 
 if __name__ == '__main__':

@@ -333,9 +333,12 @@ class DeviceScene(object):
       self.gt_mask_channels = 0 if gt_masks is None else 3 if gt_masks.ndim == 5 else 1
 
   def _padded(self, rows):
-    """uint8 [n, bytes] -> the device store [n, stride], stride = bytes rounded up to 16 (zero padding), and the stride"""
+    """uint8 [n, bytes] -> the device store [n, stride], stride = bytes rounded up to 16 (zero padding), and the stride.  Rows already on the
+    device that need no padding are adopted in place (the virtual views ``ingest.build_virtual_views`` made are not copied again)."""
     n, nbytes = rows.shape
     stride = (nbytes + 15) // 16 * 16
+    if stride == nbytes and isinstance(rows, torch.Tensor) and rows.dtype == torch.uint8 and rows.is_contiguous():  # (a tensor: _adopt found it on the device)
+      return rows, stride
     store = torch.zeros((n, stride), dtype=torch.uint8, device=self.device)
     store[:, :nbytes] = rows if isinstance(rows, torch.Tensor) else _host_tensor(rows).to(self.device)
     return store, stride

@@ -15,6 +15,8 @@ this module writes them.
 
 Resizing to the working size uses ``torch.nn.functional.interpolate`` (nearest / area / bilinear, ``align_corners=False``) where the
 reference uses cv2.resize: that step is NOT cv2-exact.  Everything after it is pinned by the tests (tests/test_gpu_virtual_views.py).
+The cv2-style path is ``dynibar_amd.ingest.build_virtual_views`` (``python -m dynibar_amd.ingest --virtual_views``): the float INTER_AREA and
+INTER_LINEAR on the device, every frame's views in one batched pass, the same poses and, for the same resized inputs, the same bytes.
 """
 from __future__ import annotations
 

@@ -575,6 +575,36 @@ int dyn_sobel_alpha(const float* x, int B, int H, int W, float beta, float* alph
  * uint8(255 clip(clip(rgb / 255, 0, 1) m, 0, 1)), m = erosion(clip(alpha, 0, 1) > 0.5, disk(1)); out-of-image neighbours do not erode */
 int dyn_vv_finish(const float* feat, int B, int C, int H, int W, uint8_t* out, void* stream);
 
+/* The virtual views of F frames x V views in one pass (render_source_vv.py:283-330 for every frame): per frame f
+ *   x = (1 / disp[f]) / 10, alpha = exp(-0.5 |sobel(x)|) as dyn_sobel_alpha, source = (255 img[f], alpha), depth = 1 / disp[f];
+ * per view b = f * V + v the forward splat of dyn_forward_splat with k_src_inv = k_inv[f], k_dst = k[f], rot[b], t[b] and the importance
+ * minimum / maximum of view b; then dyn_vv_finish.  Every value is formed by the operations of those three entries in their order and every
+ * sum runs in ascending contribution id, so out is BIT-IDENTICAL to sobel -> forward splat of the frame repeated V times -> finish; no frame
+ * is repeated in memory (view b reads frame b / V) and the splatted channels nothing reads (importance, ones) are not formed.
+ * tenth_by_division: x = depth / 10.f; 0: x = depth * (1.f / 10.f), which is what torch evaluates for `depth / 10.0` on a HIP tensor (a
+ * division by a host scalar becomes a multiplication by its fp32 reciprocal there), so 0 reproduces the script on a HIP device and 1 on a
+ * host tensor.  k_inv is the caller's inverse of k, as dyn_forward_splat takes it.  View b is written to out + b * out_pitch (BYTES),
+ * [H,W,3] contiguous; bytes between views are not written.  No host synchronisation, no device-to-host copy, nothing allocated.
+ * Workspace: DEVICE scratch of dyn_vv_frames_workspace_bytes(F,V,H,W) bytes on 16 bytes (0: unsupported: a size below 1, V > 65535 or
+ * F*V*H*W > 2^28).  Frames are sorted in groups that need no more radix passes than one frame's views; the grouping does not change a bit. */
+size_t dyn_vv_frames_workspace_bytes(int F, int V, int H, int W);
+typedef struct {
+  int F, V, H, W;
+  const float* img;          /* [F,H,W,3] in 0..1 */
+  const float* disp;         /* [F,H,W] */
+  const float* k;            /* [F,3,3] source = destination intrinsics */
+  const float* k_inv;        /* [F,3,3] */
+  const float* rot;          /* [F*V,3,3] */
+  const float* t;            /* [F*V,3] */
+  float eps;                 /* the package's eps (1e-7) */
+  int tenth_by_division;
+  uint8_t* out;
+  int64_t out_pitch;
+  void* workspace;
+  size_t workspace_bytes;
+} DynVvFramesParams;
+int dyn_vv_frames(const DynVvFramesParams* p, void* stream);
+
 /* ====== the training objective of the monocular main loop (train.py:300-456) on the dictionary render_rays_mono(is_train=True) returns =====
  * Forward: k_objective_rays (one wavefront per ray: the Charbonnier colour terms, disparity, flow, sum_S weights_dy / weights_st -> ratio ->
  * entropy and the static mask, the distortion loss by two wave scans) and k_objective_samples (one thread per sample: consistency and the
@@ -1009,6 +1039,20 @@ int dyn_adamx_step_guarded(const DynAdamXGuardedParams* p, void* stream);
  *                          at 0.f and adds (float)S[k] * alpha over the x entries in order; the destination row is the sequential sum
  *                          of beta * rowvalue over the y entries, the first term initialising it; rintf (ties to even), saturated.
  *                          Table indices are clamped to the source, counts to K.
+ *   dyn_resize_area_f32    cv2.resize(INTER_AREA) on fp32 [B,Hs,Ws,C], C in 1..4 -> [B,Hd,Wd,C], shrinking AND enlarging; dst_pitch a multiple
+ *                          of 4.  The branch is OpenCV's.  (1) Neither axis enlarges and both scales are integers (the test above): equal
+ *                          sizes are a copy, bit for bit; else sum = 0.f over the ix * iy block in row-major order k = q * ix + p, in the
+ *                          order of OpenCV's scalar loop: while four or more taps remain sum = sum + (((S[k] + S[k+1]) + S[k+2]) + S[k+3]),
+ *                          then the rest one at a time; out = sum * (1.f / (ix * iy)).  (OpenCV's 2 x 2 SIMD path may associate
+ *                          differently; the scalar order is the contract.)  (2) Neither axis enlarges, a scale is not an integer: the
+ *                          decimation tables and the arithmetic of dyn_resize_area_u8 without the rintf and the saturation.  (3) An axis
+ *                          enlarges (Hd > Hs or Wd > Ws): OpenCV's two-tap linear kernel with area-mode coefficients on BOTH axes, also the
+ *                          one that shrinks; the tables are not read.  With inv = (double)d / s and scale = 1.0 / inv, destination index i
+ *                          has s0 = floor(i * scale) in double and f = (float)((i + 1) - (s0 + 1) * inv) with the inner arithmetic in
+ *                          double, then in fp32 f = f <= 0 ? 0 : f - floorf(f).  Edges and order as dyn_resize_linear_f32: horizontally
+ *                          s0 >= Ws - 1 -> the value is S[Ws - 1], no second tap, else S[s0] * (1.f - f) + S[s0 + 1] * f; vertically rows
+ *                          s0, s0 + 1 clamped to Hs - 1, r0 * (1.f - f) + r1 * f, weights not zeroed; horizontal first, every product and
+ *                          sum rounded on its own.  Like the rest of this section a restatement of OpenCV from memory: BELIEVED, NOT VERIFIED.
  *   dyn_resize_linear_f32  cv2.resize(INTER_LINEAR) on fp32 [B,Hs,Ws] -> [B,Hd,Wd].  Per destination index i: f = (float)((i + 0.5) *
  *                          scale - 0.5) with the inner arithmetic in double, s0 = floor(f), f = f - (float)s0 in fp32.  Horizontally:
  *                          s0 < 0 -> s0 = 0, f = 0; s0 >= Ws - 1 -> the value is S[Ws - 1], no second tap; else S[s0] * (1.f - f) +
@@ -1030,6 +1074,9 @@ int dyn_adamx_step_guarded(const DynAdamXGuardedParams* p, void* stream);
 int dyn_resize_area_u8(int B, int Hs, int Ws, int C, int Hd, int Wd, const void* src, void* dst, int64_t dst_pitch, const int32_t* xcount,
                        const int32_t* xidx, const float* xw, int Kx, const int32_t* ycount, const int32_t* yidx, const float* yw, int Ky,
                        void* stream);
+int dyn_resize_area_f32(int B, int Hs, int Ws, int C, int Hd, int Wd, const float* src, float* dst, int64_t dst_pitch, const int32_t* xcount,
+                        const int32_t* xidx, const float* xw, int Kx, const int32_t* ycount, const int32_t* yidx, const float* yw, int Ky,
+                        void* stream);
 int dyn_resize_linear_f32(int B, int Hs, int Ws, int Hd, int Wd, const float* src, float* dst, int64_t dst_pitch, int reciprocal, int divide,
                           float divisor, void* stream);
 int dyn_resize_nearest(int B, int Hs, int Ws, int pixel_bytes, int Hd, int Wd, const void* src, void* dst, int64_t dst_pitch, int below,

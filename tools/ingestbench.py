@@ -3,6 +3,10 @@ process, alternating.  GPU only -- there is no CPU path.
 
   python tools/ingestbench.py [--rounds 20] [--batch 8] [--out profiles/ingest.txt]
   python tools/ingestbench.py --rocprof profiles/ingest_kernel_stats.txt     # kernel times: a separate run under rocprofv3 --kernel-trace --stats
+  python tools/ingestbench.py --virtual_views [--out profiles/ingest_virtual_views.txt]      # 16 frames x 8 views at 288 x 512: the per-frame
+      path (render_frame_virtual_views with its copy to the host) against ingest.virtual_views at batch 8 and 16, inputs on the device, median
+      of 5 runs after 2 warm-ups, a host clock around work that ends in a stream synchronise; the bytes are compared first
+  python tools/ingestbench.py --virtual_views --rounds 5 --rocprof profiles/ingest_virtual_views_kernel_stats.txt    # its kernels, a separate run
 
 Seeded inputs: frames 1080 x 1920 x 3 -> 288 x 512 (area), depth 384 x 672 -> 288 x 512 (linear), masks 1080 x 1920 -> 288 x 512 (nearest),
 erosion with r = 3 and depth bounds (5, 95) at 384 x 672, `batch` images per call.  After a warm-up each round times the ingest call and then
@@ -109,6 +113,77 @@ def loop(rounds, batch):
   torch.cuda.synchronize()
 
 
+VV_FRAMES, VV_VIEWS, VV_RUNS, VV_WARMUPS = 16, 8, 5, 2
+
+
+def vv_inputs():
+  """16 frames at 288 x 512 on the device with the script's 8 poses each (tests/vv_ingest_cases.py: a smooth image, a disparity with a step; the
+  nearest pixel shifts by about 20 px)"""
+  import vv_ingest_cases as vc
+  import ingest_cases as ic
+  img, disp, K, c2w, vsv = vc.vv_inputs(F=VV_FRAMES, H=H, W=W, shift=20.0)
+  return ic.dev_t(img, 'cuda:0'), ic.dev_t(disp, 'cuda:0'), K, c2w, vsv
+
+
+def vv_bytes_per_frame():
+  """what the kernels of dyn_vv_frames read and write per frame of 8 views, from the shapes (the sort's passes at 8 frames per call: 3)"""
+  hw, v = H * W, VV_VIEWS
+  source = hw * (3 * 4 + 9 * 4 + 16)                   # k_vv_source: img, nine disparity taps (cached: counted once each), rgba
+  project = v * hw * (4 + 12)                          # disp (once per view), flow + importance
+  keys = v * hw * (12 + 16 + 4 + 8)                    # flow + importance, 4 keys, exp(w), list bounds
+  sort = 3 * v * hw * 4 * (4 + 8 + 8)                  # per pass and contribution: histogram read, scatter read and write of (key, id)
+  bounds = v * hw * 4 * 4 + v * hw * 8
+  resolve = v * hw * (8 + 4 * (4 + 8 + 4 + 16) + 4)    # bounds, per contribution id + flow + exp(w) + rgba, the packed pixel
+  erode = v * hw * (4 + 3)
+  return dict(source=source, project=project, keys=keys, sort=sort, bounds=bounds, resolve=resolve, erode=erode,
+              total=source + project + keys + sort + bounds + resolve + erode, old_path_eightfold_fp32_buffers=v * hw * (16 + 4) * 2)
+
+
+def run_virtual_views():
+  """(a) the per-frame path, render_frame_virtual_views for each of the 16 frames with its copy to the host, against (b) ingest.virtual_views with
+  batch 8 and 16: median of 5 runs after 2 warm-ups, a host clock around work that ends in a stream synchronise, the legs alternating"""
+  import time
+  import numpy as np
+  import torch
+  from dynibar_amd import ingest, virtual_views as vv
+  img, disp, K, c2w, vsv = vv_inputs()
+  legs = {
+      'per_frame': lambda: [vv.render_frame_virtual_views(img[f], disp[f], K, c2w[f], vsv[f]) for f in range(VV_FRAMES)],
+      'batch_8': lambda: ingest.virtual_views(img, disp, K, c2w, vsv, batch=8),
+      'batch_16': lambda: ingest.virtual_views(img, disp, K, c2w, vsv, batch=16),
+  }
+  want = np.stack(legs['per_frame']())
+  for name in ('batch_8', 'batch_16'):
+    assert np.array_equal(legs[name]().cpu().numpy(), want), name  # the bytes of the path it replaces, at the size that is timed
+  st = torch.cuda.current_stream()
+  times = {k: [] for k in legs}
+  for r in range(VV_WARMUPS + VV_RUNS):
+    for name, fn in legs.items():
+      st.synchronize()
+      t0 = time.perf_counter()
+      fn()
+      st.synchronize()
+      if r >= VV_WARMUPS:
+        times[name].append((time.perf_counter() - t0) * 1e3)
+  q = lambda v: dict(median=round(statistics.median(v), 3), min=round(min(v), 3), max=round(max(v), 3), runs=[round(x, 3) for x in v])
+  out = dict(frames=VV_FRAMES, views=VV_VIEWS, size=[H, W], device=torch.cuda.get_device_name(0), fill=round(float((want.max(-1) > 0).mean()), 3),
+             ms={k: q(v) for k, v in times.items()}, bytes_per_frame=vv_bytes_per_frame())
+  a = out['ms']['per_frame']
+  out['spread_per_frame_ms'] = round(a['max'] - a['min'], 3)
+  for name in ('batch_8', 'batch_16'):
+    out[f'{name}_over_per_frame'] = round(out['ms'][name]['median'] / a['median'], 4)
+  return out
+
+
+def loop_virtual_views(rounds):
+  import torch
+  from dynibar_amd import ingest
+  img, disp, K, c2w, vsv = vv_inputs()
+  for _ in range(rounds):
+    ingest.virtual_views(img, disp, K, c2w, vsv, batch=8)
+  torch.cuda.synchronize()
+
+
 def main():
   ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
   ap.add_argument('--rounds', type=int, default=20)
@@ -116,16 +191,19 @@ def main():
   ap.add_argument('--out', default=None)
   ap.add_argument('--rocprof', default=None, help='write the rocprofv3 kernel stats of a separate run to this file')
   ap.add_argument('--loop', action='store_true', help='(internal: the child run under the profiler)')
+  ap.add_argument('--virtual_views', action='store_true',
+                  help='the virtual views of 16 frames x 8 views at 288 x 512: the per-frame path against ingest.virtual_views (with --rocprof: the '
+                       'kernels of ingest.virtual_views at batch 8)')
   a = ap.parse_args()
   if a.loop:
-    loop(a.rounds, a.batch)
+    loop_virtual_views(a.rounds) if a.virtual_views else loop(a.rounds, a.batch)
     return
   if a.rocprof:
     import glob
     import tempfile
     d = tempfile.mkdtemp(prefix='ingestbench_')
     cmd = ['rocprofv3', '--kernel-trace', '--stats', '-d', d, '--', sys.executable, os.path.abspath(__file__), '--rounds', str(a.rounds), '--batch',
-           str(a.batch), '--loop']
+           str(a.batch), '--loop'] + (['--virtual_views'] if a.virtual_views else [])
     subprocess.run(cmd, check=True, cwd=d, timeout=600)
     dbs = sorted(glob.glob(os.path.join(d, '**', '*.db'), recursive=True))
     assert dbs, f'rocprofv3 wrote no database under {d}'
@@ -133,12 +211,16 @@ def main():
                          text=True).stdout
     os.makedirs(os.path.dirname(os.path.abspath(a.rocprof)), exist_ok=True)
     with open(a.rocprof, 'w') as f:
-      f.write(f'# python tools/ingestbench.py --rounds {a.rounds} --batch {a.batch} --loop ({a.batch} images per call)\n')
+      if a.virtual_views:
+        f.write(f'# python tools/ingestbench.py --virtual_views --rounds {a.rounds} --loop ({a.rounds} calls of ingest.virtual_views: {VV_FRAMES} frames '
+                f'x {VV_VIEWS} views at {H} x {W}, batch 8)\n')
+      else:
+        f.write(f'# python tools/ingestbench.py --rounds {a.rounds} --batch {a.batch} --loop ({a.batch} images per call)\n')
       f.write('\n'.join(ln.split('   (')[0] + '   durations in microseconds' if ln.startswith('# rocprofv3') and '.db)' in ln else ln
                         for ln in txt.split('\n')))  # (the summary's header names the run's database file: not kept)
     print(txt)
     return
-  line = json.dumps(run(a.rounds, a.batch))
+  line = json.dumps(run_virtual_views() if a.virtual_views else run(a.rounds, a.batch))
   print(line)
   if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
