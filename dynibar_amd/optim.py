@@ -58,6 +58,7 @@ import ctypes
 import inspect
 import math
 import re
+import types
 
 import numpy as np
 import torch
@@ -83,6 +84,8 @@ GradStats.__doc__ = """What the last ``dyn_grad_norm`` over a table wrote (DynGr
 
 _UNBUILT = ('differentiable',)
 _EXTENDED = ('amsgrad', 'maximize', 'capturable')  # with weight_decay != 0: what sends a step through dyn_adamx_step
+_STEP_CALLS = {(False, False): ('dyn_adam_step', 'DynAdamParams'), (False, True): ('dyn_adam_step_guarded', 'DynAdamGuardedParams'),
+               (True, False): ('dyn_adamx_step', 'DynAdamXParams'), (True, True): ('dyn_adamx_step_guarded', 'DynAdamXGuardedParams')}  # by (extended, guarded)
 _increment_version = getattr(torch._C, '_increment_version', None)
 _TORCH_HAS_DECOUPLED = 'decoupled_weight_decay' in inspect.signature(torch.optim.Adam.__init__).parameters
 
@@ -101,9 +104,9 @@ def _chunk_list(sizes):
 
 
 def _new_tables(dev, sizes, extended=False):
-  """What depends on a parameter set alone: the chunk list (uploaded once), the device buffer its records go to, the partial sums and the
-  zeroed DynGradStats of the guard.  extended: the buffer holds the DynAdamTensor records (the norm reads them) and behind them the
-  DynAdamXTensor records of the same tensors, so a step is still one copy."""
+  """What depends on a parameter set alone: the chunk list (uploaded once), the device buffer its records go to with the rotation of host
+  buffers they are staged in, the partial sums and the zeroed DynGradStats of the guard.  extended: the buffers hold the DynAdamTensor
+  records (the norm reads them) and behind them the DynAdamXTensor records of the same tensors, so a step is still one copy."""
   chunks = _chunk_list(sizes)
   host = torch.from_numpy(np.ascontiguousarray(chunks))
   nbytes = max(1, len(sizes)) * (RECORD.itemsize + (XRECORD.itemsize if extended else 0))
@@ -122,12 +125,13 @@ def _new_tables(dev, sizes, extended=False):
   views = GradStats(norm=f32[at['norm'] // 4], coef=f32[at['coef'] // 4], finite=i32[at['finite'] // 4], calls=stats[at['calls'] // 8],
                     nonfinite=stats[at['nonfinite'] // 8], sumsq=stats.view(torch.float64)[at['sumsq'] // 8])
   return dict(device=dev, sizes=sizes, extended=bool(extended), n_chunks=int(len(chunks)), chunks=chunks_dev, records=records_dev, nbytes=nbytes, partials=partials,
-              stats=stats, grad_stats=views)
+              stats=stats, grad_stats=views, staging=[])  # staging: pinned host buffers of the records with the event of their last copy
 
 
-def _stage_in(staging, dev, nbytes):
+def _stage_in(tab):
   """A host buffer for the records that no earlier copy still reads: pinned, with the event of its last copy."""
-  if dev.type != 'cuda':
+  staging, nbytes = tab['staging'], tab['nbytes']
+  if tab['device'].type != 'cuda':
     if not staging:
       staging.append((torch.empty((nbytes,), dtype=torch.uint8), None))
     return staging[0]
@@ -139,14 +143,54 @@ def _stage_in(staging, dev, nbytes):
   return entry
 
 
-def _send(tab, host, event, dev):
-  """The records of this call to the device, asynchronously on the current stream -> the tensor the kernels read them from."""
-  if dev.type != 'cuda':
-    return host
-  with torch.cuda.device(dev):
-    tab['records'].copy_(host, non_blocking=True)
-    event.record(torch.cuda.current_stream(dev))
-  return tab['records']
+def _records(host, pointers, sizes, skip):
+  """The first len(sizes) DynAdamTensor rows of a staging buffer from the pointers (field -> one per tensor), the sizes and the skip
+  flags; every other field is 0 and the caller's to fill -> the rows"""
+  rec = host.numpy()[:len(sizes) * RECORD.itemsize].view(RECORD)
+  rec[:] = 0
+  for k, column in pointers.items():
+    rec[k] = column
+  rec['n'], rec['skip'] = sizes, skip
+  return rec
+
+
+def _send(tab, host, event):
+  """The records of this call to the device, asynchronously on the current stream -> the call's fields that every entry point takes"""
+  dev, records = tab['device'], host
+  if dev.type == 'cuda':
+    records = tab['records']
+    with torch.cuda.device(dev):
+      records.copy_(host, non_blocking=True)
+      event.record(torch.cuda.current_stream(dev))
+  return dict(tensors=ctypes.c_void_p(records.data_ptr()), n_tensors=len(tab['sizes']), chunks=ctypes.c_void_p(tab['chunks'].data_ptr()),
+              n_chunks=tab['n_chunks'])
+
+
+def _contiguous(g, copies):
+  """A contiguous copy of a strided g, with (g, copy) remembered: what a kernel writes to the copy, the caller owes the original."""
+  copies.append((g, g.contiguous()))
+  return copies[-1][1]
+
+
+def _check_gradient(g, who, name, *args):
+  """What every entry point refuses about a gradient itself; name(*args) names its parameter in the caller's words."""
+  if g.is_sparse or g.layout != torch.strided:
+    raise RuntimeError(f'{who}: the gradient of {name(*args)} is sparse; sparse gradients are not built')
+  if g.dtype != torch.float32:
+    raise TypeError(f'{who}: the gradient of {name(*args)} is {str(g.dtype).replace("torch.", "")}, not float32')
+
+
+def _one_device(tensors, dev, who, what, name):
+  """... and about where tensors are: on a HIP device, all on the one of the tensors before them (dev, None in front of the first) -> that
+  device; name(i) names tensors[i]."""
+  for i, t in enumerate(tensors):
+    if _lib._REQUIRE_DEVICE and not t.is_cuda:
+      raise RuntimeError(f'{who} needs {what} on a HIP device (cuda:N), there is no CPU fallback; {name(i)} is on {t.device}')
+    if dev is None:
+      dev = t.device
+    elif t.device != dev:
+      raise RuntimeError(f'{who}: {what} on more than one device: {name(i)} is on {t.device}, others on {dev} (one HIP device)')
+  return dev
 
 
 def _check_max_norm(value, who, what):
@@ -205,8 +249,7 @@ class AdamX(torch.optim.Optimizer):
                     capturable=capturable, differentiable=differentiable, fused=None)
     if _TORCH_HAS_DECOUPLED or decoupled_weight_decay:
       defaults['decoupled_weight_decay'] = bool(decoupled_weight_decay)
-    self._tables = None     # what depends on the parameter set alone: sizes, the chunk list on the device, the device buffer of the records
-    self._staging = []      # pinned host buffers of the records with the event of their last copy
+    self._tables = None     # what depends on the parameter set alone (_new_tables), the staging buffers of its records included
     self._cleared = {}      # id(parameter) -> (gradient tensor, its version) as the last step(zero_grads=True) left it
     self._grad_stats = None  # the views into the tables' DynGradStats, once a guarded step has written them
     super().__init__(params, defaults)
@@ -233,7 +276,6 @@ class AdamX(torch.optim.Optimizer):
 
   def __setstate__(self, state):
     super().__setstate__(state)
-    self.__dict__.setdefault('_staging', [])
     self.__dict__.setdefault('_cleared', {})
     self._tables = None
     self._grad_stats = None
@@ -300,8 +342,9 @@ class AdamX(torch.optim.Optimizer):
 
   # ---- the step ------------------------------------------------------------------------------------------------------------------------
   def _collect(self):
-    """Every check that can refuse, before anything is changed or launched -> (device, [(group index, parameter, gradient or None)])."""
-    entries, dev = [], None
+    """Every check that can refuse, before anything is changed or launched -> (device, [(group index, parameter, gradient or None,
+    the state of a parameter with a gradient or None before its first step)])."""
+    entries = []
     for gi, group in enumerate(self.param_groups):
       self._check_group(group, gi)
       moments = ('exp_avg', 'exp_avg_sq', 'max_exp_avg_sq') if group.get('amsgrad', False) else ('exp_avg', 'exp_avg_sq')
@@ -314,12 +357,9 @@ class AdamX(torch.optim.Optimizer):
           raise ValueError(f'dynibar_amd.optim.Adam: {_name(gi, pi, p)} is not contiguous')
         if p.numel() >= 2 ** 31:
           raise ValueError(f'dynibar_amd.optim.Adam: {_name(gi, pi, p)} has {p.numel()} elements (below 2^31 per tensor)')
-        g = p.grad
+        g, st = p.grad, None
         if g is not None:
-          if g.is_sparse or g.layout != torch.strided:
-            raise RuntimeError(f'dynibar_amd.optim.Adam: the gradient of {_name(gi, pi, p)} is sparse; sparse gradients are not built')
-          if g.dtype != torch.float32:
-            raise TypeError(f'dynibar_amd.optim.Adam: the gradient of {_name(gi, pi, p)} is {str(g.dtype).replace("torch.", "")}, not float32')
+          _check_gradient(g, 'dynibar_amd.optim.Adam', _name, gi, pi, p)
           if g.shape != p.shape or g.device != p.device:
             raise ValueError(f'dynibar_amd.optim.Adam: the gradient of {_name(gi, pi, p)} is {tuple(g.shape)} on {g.device}, '
                              f'its parameter is on {p.device}')
@@ -330,75 +370,67 @@ class AdamX(torch.optim.Optimizer):
               if m.dtype != torch.float32 or m.shape != p.shape or m.device != p.device or not m.is_contiguous():
                 raise ValueError(f'dynibar_amd.optim.Adam: {key} of {_name(gi, pi, p)} must be contiguous float32 {tuple(p.shape)} on {p.device}, '
                                  f'got {str(m.dtype).replace("torch.", "")} {tuple(m.shape)} on {m.device}')
-        entries.append((gi, p, g))
-    for gi, group in enumerate(self.param_groups):  # where the tensors are, after what they are
-      for pi, p in enumerate(group['params']):
-        if _lib._REQUIRE_DEVICE and not p.is_cuda:
-          raise RuntimeError(f'dynibar_amd.optim.Adam needs parameters on a HIP device (cuda:N), there is no CPU fallback; {_name(gi, pi, p)} is on {p.device}')
-        if dev is None:
-          dev = p.device
-        elif p.device != dev:
-          raise RuntimeError(f'dynibar_amd.optim.Adam: parameters on more than one device: {_name(gi, pi, p)} is on {p.device}, others on {dev} (one HIP device)')
-    return dev, entries
+        entries.append((gi, p, g, st))
 
-  def _make_tables(self, dev, sizes, extended=False):
-    """The chunk list of a parameter set (uploaded once), the device buffer its records go to and the guard's buffers."""
-    self._staging = []
-    self._grad_stats = None
-    self._tables = _new_tables(dev, sizes, extended)
+    def name(i):  # (the entries are in the groups' order)
+      gi, p = entries[i][:2]
+      return _name(gi, i - sum(len(group['params']) for group in self.param_groups[:gi]), p)
+    # where the tensors are, after what they are
+    return _one_device([e[1] for e in entries], None, 'dynibar_amd.optim.Adam', 'parameters', name), entries
 
-  def _stage(self, dev, nbytes):
-    return _stage_in(self._staging, dev, nbytes)
+  @property
+  def _staging(self):
+    return self._tables['staging'] if self._tables else []
 
   @property
   def grad_stats(self):
     """``GradStats`` of the last guarded step (device tensor views; reading one synchronises), None before the first."""
     return self.__dict__.get('_grad_stats')
 
-  @torch.no_grad()
-  def step(self, closure=None, zero_grads=False, max_grad_norm=None, skip_nonfinite=False):
-    """One ``k_adam_step`` launch over every parameter that has a gradient.  zero_grads: the launch also stores 0 to the gradients it read.
-    max_grad_norm (a finite number above 0) and / or skip_nonfinite: the guarded step of the module docstring, three launches."""
-    guarded = max_grad_norm is not None or bool(skip_nonfinite)
-    if max_grad_norm is not None:
-      max_grad_norm = _check_max_norm(max_grad_norm, 'dynibar_amd.optim.Adam', 'max_grad_norm')
-    loss = None
-    if closure is not None:
-      with torch.enable_grad():
-        loss = closure()
-    dev, entries = self._collect()
-    self._cleared = {}
-    if dev is None or all(g is None for _, _, g in entries):
-      return loss
-    sizes = [p.numel() for _, p, _ in entries]
+  def _tables_for(self, dev, sizes):
+    """The tables of this parameter set on this device, made anew when one of the two changes or the step changes kernels."""
     # the plain kernels unless a group asks for what only the extended step has: defaults change nothing
     extended = bool(self.extended_kernel) or any(g.get('weight_decay', 0) != 0 or any(g.get(o, False) for o in _EXTENDED) for g in self.param_groups)
-    if self._tables is None or self._tables['device'] != dev or self._tables['sizes'] != sizes or self._tables['extended'] != extended:
-      self._make_tables(dev, sizes, extended)
     tab = self._tables
-    if tab['n_chunks'] == 0:
-      return loss
-    n = len(entries)
-    ptr = {k: [0] * n for k in (('p', 'g', 'm', 'v', 'vmax', 'pow', 'step') if extended else 'pgmv')}
-    a, s2, skip = [0.0] * n, [0.0] * n, [1] * n
-    scalars, copies, cleared, stepped, advance = {}, [], {}, [], 0
-    per_group, consts = [], []  # what a group's options come to, once per step and not once per tensor
+    if tab is None or tab['device'] != dev or tab['sizes'] != sizes or tab['extended'] != extended:
+      self._grad_stats = None
+      tab = self._tables = _new_tables(dev, sizes, extended)
+    return tab
+
+  def _group_constants(self):
+    """What a group's options come to, once per step and not once per tensor -> ([(group, lr, beta1, beta2, capturable, amsgrad)],
+    float64 [groups, 10]: c1, c2, beta2, eps; wd, decay, flags; lr, beta1, beta2 for the device's scalars)"""
+    per_group, consts = [], []
     for group in self.param_groups:
       lr, (beta1, beta2), lam = group['lr'], group['betas'], group.get('weight_decay', 0)
       decoupled = lam != 0 and bool(group.get('decoupled_weight_decay', False))
       per_group.append((group, lr, beta1, beta2, bool(group.get('capturable', False)), bool(group.get('amsgrad', False))))
-      # c1, c2, beta2, eps; wd, decay (the factor in double here, fp32 in the record: rounded once), flags; lr, beta1, beta2 for the device's scalars
+      # (the decoupled factor in double here, fp32 in the record: rounded once)
       consts.append((1 - beta1, 1 - beta2, beta2, group['eps'], 0.0 if decoupled else lam, 1 - lr * lam if decoupled else 1.0,
                      1 if group.get('maximize', False) else 0, lr, beta1, beta2))
-    for i, (gi, p, g) in enumerate(entries):
+    return per_group, np.array(consts, np.float64)
+
+  @staticmethod
+  def _first_state(st, p, capturable):
+    """torch's layout of a first-seen parameter's state (max_exp_avg_sq and beta_pow are made where a step first needs them)"""
+    st['step'] = torch.zeros((), dtype=torch.float32, device=p.device) if capturable else torch.tensor(0.0, dtype=torch.float32)
+    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+    st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+  def _columns(self, entries, sizes, per_group, extended, zero_grads):
+    """Every tensor that steps: its state, its count advanced where the host keeps it, the pointers and scalars of its record -> the records'
+    columns (ptr, a, s2, skip, advance) and what the bookkeeping after the launch needs (copies, cleared, stepped)"""
+    n = len(entries)
+    ptr = {k: [0] * n for k in (('p', 'g', 'm', 'v', 'vmax', 'pow', 'step') if extended else 'pgmv')}
+    a, s2, skip = [0.0] * n, [0.0] * n, [1] * n
+    scalars, copies, cleared, stepped, advance = {}, [], {}, [], 0
+    for i, (gi, p, g, st) in enumerate(entries):
       if g is None or sizes[i] == 0:
         continue
       group, lr, beta1, beta2, capturable, amsgrad = per_group[gi]
-      st = self.state[p]
-      if len(st) == 0:  # torch's layout of a first-seen parameter
-        st['step'] = torch.zeros((), dtype=torch.float32, device=p.device) if capturable else torch.tensor(0.0, dtype=torch.float32)
-        st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+      if not st:
+        st = self.state[p]
+        self._first_state(st, p, capturable)
       if capturable:  # the count lives on the device: k_adam_advance is its only writer, a held step leaves it alone
         self._device_counts(st, p, group)
         ptr['pow'][i], ptr['step'][i] = st['beta_pow'].data_ptr(), st['step'].data_ptr()
@@ -416,51 +448,79 @@ class AdamX(torch.optim.Optimizer):
         if 'max_exp_avg_sq' not in st:
           st['max_exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
         ptr['vmax'][i] = st['max_exp_avg_sq'].data_ptr()
-      gc = g if g.is_contiguous() else g.contiguous()
-      if gc is not g:
-        copies.append((g, gc))  # (kept alive until the launch is enqueued; cleared below when the kernel clears its copy)
+      gc = g if g.is_contiguous() else _contiguous(g, copies)  # (a copy lives until the launch is enqueued)
       ptr['p'][i], ptr['g'][i], ptr['m'][i], ptr['v'][i] = p.data_ptr(), gc.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr()
       skip[i] = 0
       stepped.append(p)
       if zero_grads:
         cleared[id(p)] = g
-    host, event = self._stage(dev, tab['nbytes'])
-    rec = host.numpy()[:n * RECORD.itemsize].view(RECORD)
-    for k in 'pgmv':
-      rec[k] = ptr[k]
-    const = np.array(consts, np.float64)[[gi for gi, _, _ in entries]]  # [n, 10]: each tensor's group constants
-    rec['n'], rec['a'], rec['s2'], rec['skip'], rec['reserved'] = sizes, a, s2, skip, 0
+    return types.SimpleNamespace(ptr=ptr, a=a, s2=s2, skip=skip, advance=advance, copies=copies, cleared=cleared, stepped=stepped)
+
+  @staticmethod
+  def _fill(host, entries, sizes, w, consts, extended):
+    """The records of this step into a staging buffer: DynAdamTensor rows and, for the extended step, the DynAdamXTensor rows behind them."""
+    n = len(entries)
+    rec = _records(host, {k: w.ptr[k] for k in 'pgmv'}, sizes, w.skip)
+    const = consts[[e[0] for e in entries]]  # [n, 10]: each tensor's group constants
+    rec['a'], rec['s2'] = w.a, w.s2
     rec['c1'], rec['c2'], rec['beta2'], rec['eps'] = const[:, 0], const[:, 1], const[:, 2], const[:, 3]
     if extended:
       xrec = host.numpy()[n * RECORD.itemsize:n * (RECORD.itemsize + XRECORD.itemsize)].view(XRECORD)
       for k in RECORD.names[:-1]:
         xrec[k] = rec[k]
       for k in ('vmax', 'pow', 'step'):
-        xrec[k] = ptr[k]
+        xrec[k] = w.ptr[k]
       xrec['wd'], xrec['decay'], xrec['flags'], xrec['lr_d'], xrec['beta1_d'], xrec['beta2_d'] = (const[:, j] for j in range(4, 10))
-    records = _send(tab, host, event, dev)
-    like = entries[0][1]
-    table = dict(tensors=ctypes.c_void_p(records.data_ptr()), n_tensors=n, chunks=ctypes.c_void_p(tab['chunks'].data_ptr()), n_chunks=tab['n_chunks'])
-    xtable = dict(table, tensors=ctypes.c_void_p(records.data_ptr() + n * RECORD.itemsize), zero_grads=1 if zero_grads else 0, advance=advance)
+
+  def _launch(self, tab, table, like, advance, zero_grads, guarded, max_grad_norm, skip_nonfinite):
+    """dyn_grad_norm in front of a guarded step, then the one entry point of (extended, guarded)."""
+    stream, extended = stream_of(like), tab['extended']
+    fields = dict(table, zero_grads=1 if zero_grads else 0)
+    if extended:  # its records lie behind the plain ones, which the norm reads
+      fields.update(tensors=ctypes.c_void_p(table['tensors'].value + table['n_tensors'] * RECORD.itemsize), advance=advance)
     if guarded:
       stats = ctypes.c_void_p(tab['stats'].data_ptr())
       call('dyn_grad_norm', params('DynGradNormParams', partials=ctypes.c_void_p(tab['partials'].data_ptr()), stats=stats,
-                                   max_norm=0.0 if max_grad_norm is None else max_grad_norm, count=1, **table), stream_of(like))
-      if extended:
-        call('dyn_adamx_step_guarded', params('DynAdamXGuardedParams', skip_nonfinite=1 if skip_nonfinite else 0, stats=stats, **xtable), stream_of(like))
-      else:
-        call('dyn_adam_step_guarded', params('DynAdamGuardedParams', zero_grads=1 if zero_grads else 0, skip_nonfinite=1 if skip_nonfinite else 0,
-                                             stats=stats, **table), stream_of(like))
+                                   max_norm=0.0 if max_grad_norm is None else max_grad_norm, count=1, **table), stream)
+      fields.update(skip_nonfinite=1 if skip_nonfinite else 0, stats=stats)
+    entry, struct = _STEP_CALLS[extended, guarded]
+    call(entry, params(struct, **fields), stream)
+    if guarded:
       self._grad_stats = tab['grad_stats']
-    elif extended:
-      call('dyn_adamx_step', params('DynAdamXParams', **xtable), stream_of(like))
-    else:
-      call('dyn_adam_step', params('DynAdamParams', zero_grads=1 if zero_grads else 0, **table), stream_of(like))
-    _written(stepped)  # the kernel wrote the parameters through raw pointers
+
+  def _after(self, w, zero_grads):
+    """The kernel wrote the parameters through raw pointers, and with zero_grads the gradients it read."""
+    _written(w.stepped)
     if zero_grads:
-      for g, _ in copies:  # the kernel cleared the contiguous copy, not the strided gradient itself
+      for g, _ in w.copies:  # the kernel cleared the contiguous copy, not the strided gradient itself
         g.zero_()
-      self._cleared = {k: (g, g._version) for k, g in cleared.items()}
+      self._cleared = {k: (g, g._version) for k, g in w.cleared.items()}
+
+  @torch.no_grad()
+  def step(self, closure=None, zero_grads=False, max_grad_norm=None, skip_nonfinite=False):
+    """One ``k_adam_step`` launch over every parameter that has a gradient.  zero_grads: the launch also stores 0 to the gradients it read.
+    max_grad_norm (a finite number above 0) and / or skip_nonfinite: the guarded step of the module docstring, three launches."""
+    guarded = max_grad_norm is not None or bool(skip_nonfinite)
+    if max_grad_norm is not None:
+      max_grad_norm = _check_max_norm(max_grad_norm, 'dynibar_amd.optim.Adam', 'max_grad_norm')
+    loss = None
+    if closure is not None:
+      with torch.enable_grad():
+        loss = closure()
+    dev, entries = self._collect()
+    self._cleared = {}
+    if dev is None or all(e[2] is None for e in entries):
+      return loss
+    sizes = [e[1].numel() for e in entries]
+    tab = self._tables_for(dev, sizes)
+    if tab['n_chunks'] == 0:
+      return loss
+    per_group, consts = self._group_constants()
+    w = self._columns(entries, sizes, per_group, tab['extended'], zero_grads)
+    host, event = _stage_in(tab)
+    self._fill(host, entries, sizes, w, consts, tab['extended'])
+    self._launch(tab, _send(tab, host, event), entries[0][1], w.advance, zero_grads, guarded, max_grad_norm, skip_nonfinite)
+    self._after(w, zero_grads)
     return loss
 
 
@@ -502,7 +562,7 @@ class AdamW(AdamX):
 
 
 # ---- the norm and the clip on their own ----------------------------------------------------------------------------------------------
-_TABLES = collections.OrderedDict()  # (device, sizes) -> tables and their staging buffers, for grad_norm / clip_grad_norm_
+_TABLES = collections.OrderedDict()  # (device, sizes) -> tables, for grad_norm / clip_grad_norm_
 _TABLES_KEPT = 8
 _NONFINITE = ('The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot be clipped. To disable this error and scale '
               'the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`')
@@ -517,18 +577,10 @@ def _gradients(parameters, who):
     g = p.grad
     if g is None:
       continue
-    if g.is_sparse or g.layout != torch.strided:
-      raise RuntimeError(f'{who}: the gradient of parameter {i} {tuple(p.shape)} is sparse; sparse gradients are not built')
-    if g.dtype != torch.float32:
-      raise TypeError(f'{who}: the gradient of parameter {i} {tuple(p.shape)} is {str(g.dtype).replace("torch.", "")}, not float32')
+    _check_gradient(g, who, lambda: f'parameter {i} {tuple(p.shape)}')
     if g.numel() >= 2 ** 31:
       raise ValueError(f'{who}: the gradient of parameter {i} has {g.numel()} elements (below 2^31 per tensor)')
-    if _lib._REQUIRE_DEVICE and not g.is_cuda:
-      raise RuntimeError(f'{who} needs gradients on a HIP device (cuda:N), there is no CPU fallback; that of parameter {i} is on {g.device}')
-    if dev is None:
-      dev = g.device
-    elif g.device != dev:
-      raise RuntimeError(f'{who}: gradients on more than one device: that of parameter {i} is on {g.device}, others on {dev} (one HIP device)')
+    dev = _one_device((g,), dev, who, 'gradients', lambda _: f'that of parameter {i}')
     grads.append(g)
   return dev, grads
 
@@ -539,22 +591,15 @@ def _norm_of(grads, dev, max_norm):
   key = (str(dev), tuple(sizes))
   tab = _TABLES.get(key)
   if tab is None:
-    tab = _TABLES[key] = dict(_new_tables(dev, sizes), staging=[])
+    tab = _TABLES[key] = _new_tables(dev, sizes)
     while len(_TABLES) > _TABLES_KEPT:
       _TABLES.popitem(last=False)
   else:
     _TABLES.move_to_end(key)
-  n, copies = len(grads), []
-  host, event = _stage_in(tab['staging'], dev, tab['nbytes'])
-  rec = host.numpy()[:n * RECORD.itemsize].view(RECORD)
-  rec[:] = 0
-  for i, g in enumerate(grads):
-    gc = g if g.is_contiguous() else g.contiguous()
-    if gc is not g:
-      copies.append((g, gc))
-    rec['g'][i], rec['n'][i], rec['skip'][i] = gc.data_ptr(), sizes[i], 1 if sizes[i] == 0 else 0
-  records = _send(tab, host, event, dev)
-  table = dict(tensors=ctypes.c_void_p(records.data_ptr()), n_tensors=n, chunks=ctypes.c_void_p(tab['chunks'].data_ptr()), n_chunks=tab['n_chunks'])
+  copies = []
+  host, event = _stage_in(tab)
+  _records(host, {'g': [(g if g.is_contiguous() else _contiguous(g, copies)).data_ptr() for g in grads]}, sizes, [1 if n == 0 else 0 for n in sizes])
+  table = _send(tab, host, event)
   call('dyn_grad_norm', params('DynGradNormParams', partials=ctypes.c_void_p(tab['partials'].data_ptr()),
                                stats=ctypes.c_void_p(tab['stats'].data_ptr()), max_norm=max_norm, count=1, **table), stream_of(grads[0]))
   return tab, table, copies
