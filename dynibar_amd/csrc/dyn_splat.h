@@ -16,6 +16,11 @@
 //   k_splat_radix_*   ceil(bits(B * H * W) / 8) stable passes of 8 bits: tile histogram, exclusive scan (chunks, then chunk sums), scatter
 //   k_splat_bounds    start / end of every destination's run in the sorted keys
 //   k_splat_resolve   one lane per (output pixel, group of 8 channels): the sums, and num / (den + eps) for the normalised forms
+//
+// Two chains render virtual views: one frame per call (dyn_sobel_alpha, dyn_forward_splat, dyn_vv_finish) and many frames per call
+// (dyn_vv_frames, below).  Their bytes are equal because each piece of arithmetic is stated once and both chains go through it:
+// k_splat_project<> (the projection), sobel_alpha (the foreground alpha), splat_walk (a destination's contributions, in list order),
+// vv_disk1 and vv_byte (the epilogue), and on the host splat_project_sort (clear min / max, project, keys, sort).
 #pragma once
 
 #define SPLAT_THREADS 256
@@ -69,21 +74,24 @@ __device__ __forceinline__ float splat_unord(unsigned e) { return __uint_as_floa
 // P = depth * K_src^-1 [x y 1]^T, Q = K_dst (R P + t); pix = Q.xy / clamp(Q.z, 1e-8); flow = pix - (x, y); importance = 1 / Q.z.
 // grid (<= SPLAT_PROJECT_BLOCKS, B), grid-stride over the pixels of batch entry blockIdx.y.  minmax[2b] = ord(max), minmax[2b + 1] = ord(-min),
 // zeroed first; one pair of integer atomics per workgroup (same-address atomics serialise: one pair per wave cost 0.42 ms at 8 x 288 x 512).
+// Batch entry b reads the depth plane and the two intrinsics of frame b / V: V = 1 gives every entry its own (dyn_forward_splat), V views
+// share those of their frame (dyn_vv_frames).  RECIP: the plane holds disparities and the depth is 1 / disparity.
 #define SPLAT_PROJECT_BLOCKS 32
+template <bool RECIP>
 __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_project(const float* __restrict__ depth, const float* __restrict__ kinv,
                                                                  const float* __restrict__ rot, const float* __restrict__ kdst,
-                                                                 const float* __restrict__ tr, int H, int W, float* __restrict__ flow,
+                                                                 const float* __restrict__ tr, int H, int W, int V, float* __restrict__ flow,
                                                                  float* __restrict__ imp, unsigned* __restrict__ minmax) {
-  const int b = blockIdx.y;
+  const int b = blockIdx.y, f = b / V;
   const long HW = (long)H * W;
-  const float* Ki = kinv + b * 9;
+  const float* Ki = kinv + f * 9;
   const float* Rm = rot + b * 9;
-  const float* Kd = kdst + b * 9;
+  const float* Kd = kdst + f * 9;
   const float* tv = tr + b * 3;
   float hi = -INFINITY, nlo = -INFINITY;
   for (long p = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x; p < HW; p += (long)gridDim.x * SPLAT_THREADS) {
     const int y = (int)(p / W), x = (int)(p - (long)y * W);
-    const float xf = (float)x, yf = (float)y, d = depth[b * HW + p];
+    const float xf = (float)x, yf = (float)y, d = RECIP ? 1.f / depth[f * HW + p] : depth[f * HW + p];
     float P[3], S[3], Q[3];
     for (int i = 0; i < 3; ++i) P[i] = ((d * Ki[i * 3]) * xf + (d * Ki[i * 3 + 1]) * yf) + (d * Ki[i * 3 + 2]);
     for (int i = 0; i < 3; ++i) S[i] = ((Rm[i * 3] * P[0] + Rm[i * 3 + 1] * P[1]) + Rm[i * 3 + 2] * P[2]) + tv[i];
@@ -273,17 +281,39 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_bounds(const unsigned* 
   if (i == M - 1 || keys[i + 1] != k) end[k] = (int)(i + 1);
 }
 
-struct SplatResolveArgs {
-  int C, H, W;             // frame channels (forward form: channels of src)
-  const float* frame;      // generic: [B,C,H,W]; forward: src [B,H,W,C] channels-last, then the importance and a ones channel
-  const float* imp;        // forward form: [B,H,W]
+// what the walk of a destination's contributions reads: the head of every resolve kernel's arguments
+struct SplatLists {
+  int H, W;
   const float* flow;       // [B,2,H,W]
   const float* mult;       // [B,H,W] or NULL (= 1, and the frame is not multiplied)
-  int normalize;
   float eps;
   const unsigned* ids;     // contribution ids in (destination, id) order
   const int* start;
   const int* end;
+};
+
+// The contributions of destination i = b * H * W + p, in list order (ascending id): each(w, m, src, sp) with the corner's bilinear weight,
+// the multiplier, and the source pixel as b * H * W + sp.  The weight is recomputed from the source pixel's flow as k_splat_keys formed it.
+template <class Each>
+__device__ __forceinline__ void splat_walk(const SplatLists& l, int b, long i, Each each) {
+  const long HW = (long)l.H * l.W;
+  const int s = l.start[i], e = l.end[i];
+  for (int k = s; k < e; ++k) {
+    const unsigned id = l.ids[k];
+    const long src = (long)(id >> 2);
+    const long sp = src - b * HW;
+    const int sy = (int)(sp / l.W), sx = (int)(sp - (long)sy * l.W);
+    const SplatTap t = splat_tap(sx, sy, l.flow[(b * 2) * HW + sp], l.flow[(b * 2 + 1) * HW + sp], l.H, l.W);
+    each(splat_corner_weight(t, (int)(id & 3u)), l.mult ? l.mult[src] : 1.f, src, sp);
+  }
+}
+
+struct SplatResolveArgs {
+  SplatLists l;
+  int C;                   // frame channels (forward form: channels of src)
+  const float* frame;      // generic: [B,C,H,W]; forward: src [B,H,W,C] channels-last, then the importance and a ones channel
+  const float* imp;        // forward form: [B,H,W]
+  int normalize;
   float* out;              // generic: [B,C,H,W]; forward: feat [B,C,H,W]
   float* disp;             // forward: [B,1,H,W]
   float* mask;             // forward: [B,1,H,W] or NULL
@@ -294,7 +324,7 @@ struct SplatResolveArgs {
 template <bool FWD>
 __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_resolve(SplatResolveArgs a) {
   const int b = blockIdx.z;
-  const long HW = (long)a.H * a.W;
+  const long HW = (long)a.l.H * a.l.W;
   const long p = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x;
   if (p >= HW) return;
   const int cout = FWD ? a.C + 2 : a.C;
@@ -305,15 +335,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_resolve(SplatResolveArg
 #pragma unroll
   for (int j = 0; j < SPLAT_GROUP; ++j) num[j] = 0.f;
   float den = 0.f;
-  const int s = a.start[i], e = a.end[i];
-  for (int k = s; k < e; ++k) {
-    const unsigned id = a.ids[k];
-    const long src = (long)(id >> 2);
-    const long sp = src - b * HW;
-    const int sy = (int)(sp / a.W), sx = (int)(sp - (long)sy * a.W);
-    const SplatTap t = splat_tap(sx, sy, a.flow[(b * 2) * HW + sp], a.flow[(b * 2 + 1) * HW + sp], a.H, a.W);
-    const float w = splat_corner_weight(t, (int)(id & 3u));
-    const float m = a.mult ? a.mult[src] : 1.f;
+  splat_walk(a.l, b, i, [&](float w, float m, long src, long sp) {
 #pragma unroll
     for (int j = 0; j < SPLAT_GROUP; ++j) {
       if (j < nc) {
@@ -321,17 +343,17 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_resolve(SplatResolveArg
         float f;
         if (FWD) f = c < a.C ? a.frame[src * a.C + c] : (c == a.C ? a.imp[src] : 1.f);
         else f = a.frame[((long)b * a.C + c) * HW + sp];
-        if (a.mult) f = f * m;
+        if (a.l.mult) f = f * m;
         num[j] += w * f;
       }
     }
     if (a.normalize) den += w * m;
-  }
+  });
 #pragma unroll
   for (int j = 0; j < SPLAT_GROUP; ++j) {
     if (j < nc) {
       const int c = c0 + j;
-      const float v = a.normalize ? num[j] / (den + a.eps) : num[j];
+      const float v = a.normalize ? num[j] / (den + a.l.eps) : num[j];
       if (!FWD || c < a.C) a.out[((long)b * a.C + c) * HW + p] = v;
       else if (c == a.C) a.disp[i] = v;
       else if (a.mask) a.mask[i] = v;
@@ -339,7 +361,17 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_resolve(SplatResolveArg
   }
 }
 
-// kornia.filters.spatial_gradient(mode='sobel', normalized=False) with replicate padding, alpha = exp(-beta * |grad|)  (:118-128)
+// kornia.filters.spatial_gradient(mode='sobel', normalized=False) with replicate padding, alpha = exp(-beta * |grad|)  (:118-128), at
+// (y, xx) of an H x W plane whose value at (row, column) is v(row, column)
+template <class Tap>
+__device__ __forceinline__ float sobel_alpha(int y, int xx, int H, int W, float beta, Tap v) {
+  const int ym = y > 0 ? y - 1 : 0, yp = y < H - 1 ? y + 1 : H - 1;
+  const int xm = xx > 0 ? xx - 1 : 0, xp = xx < W - 1 ? xx + 1 : W - 1;
+  const float gx = ((v(ym, xp) - v(ym, xm)) + 2.f * (v(y, xp) - v(y, xm))) + (v(yp, xp) - v(yp, xm));
+  const float gy = ((v(yp, xm) - v(ym, xm)) + 2.f * (v(yp, xx) - v(ym, xx))) + (v(yp, xp) - v(ym, xp));
+  return expf(-beta * sqrtf(gx * gx + gy * gy));
+}
+
 __global__ __launch_bounds__(SPLAT_THREADS) void k_sobel_alpha(const float* __restrict__ x, long n, int H, int W, float beta,
                                                                float* __restrict__ alpha) {
   const long i = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x;
@@ -348,16 +380,27 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_sobel_alpha(const float* __re
   const long b = i / HW, p = i - b * HW;
   const int y = (int)(p / W), xx = (int)(p - (long)y * W);
   const float* img = x + b * HW;
-  const int ym = y > 0 ? y - 1 : 0, yp = y < H - 1 ? y + 1 : H - 1;
-  const int xm = xx > 0 ? xx - 1 : 0, xp = xx < W - 1 ? xx + 1 : W - 1;
-  auto v = [&](int yy, int x2) { return img[(long)yy * W + x2]; };
-  const float gx = ((v(ym, xp) - v(ym, xm)) + 2.f * (v(y, xp) - v(y, xm))) + (v(yp, xp) - v(yp, xm));
-  const float gy = ((v(yp, xm) - v(ym, xm)) + 2.f * (v(yp, xx) - v(ym, xx))) + (v(yp, xp) - v(ym, xp));
-  alpha[i] = expf(-beta * sqrtf(gx * gx + gy * gy));
+  alpha[i] = sobel_alpha(y, xx, H, W, beta, [&](int yy, int x2) { return img[(long)yy * W + x2]; });
 }
 
-// per-view epilogue (:313-330): rgb = clip(feat[0:3] / 255, 0, 1); m = erosion(clip(feat[3], 0, 1) > 0.5, disk(1)) with out-of-image
-// neighbours not eroding; out [B,H,W,3] = uint8(255 * clip(rgb * m, 0, 1)) (truncation)
+// The per-view epilogue (:313-330): rgb = clip(feat[0:3] / 255, 0, 1); m = erosion(clip(feat[3], 0, 1) > 0.5, disk(1)) with out-of-image
+// neighbours not eroding; out [B,H,W,3] = uint8(255 * clip(rgb * m, 0, 1)) (truncation).
+// vv_disk1: the erosion at (y, x): the pixel and its in-image neighbours are all set; set(d) is the pixel d elements from this one.
+template <class Set>
+__device__ __forceinline__ bool vv_disk1(int y, int x, int H, int W, Set set) {
+  bool m = set(0);
+  if (y > 0) m = m && set(-W);
+  if (y < H - 1) m = m && set(W);
+  if (x > 0) m = m && set(-1);
+  if (x < W - 1) m = m && set(1);
+  return m;
+}
+__device__ __forceinline__ unsigned vv_byte(float feat, float m) {
+  float v = fminf(fmaxf(feat / 255.f, 0.f), 1.f);
+  v = 255.f * fminf(fmaxf(v * m, 0.f), 1.f);
+  return (unsigned)(int)v;
+}
+
 __global__ __launch_bounds__(SPLAT_THREADS) void k_vv_finish(const float* __restrict__ feat, long n, int C, int H, int W,
                                                              unsigned char* __restrict__ out) {
   const long i = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x;
@@ -366,32 +409,24 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_vv_finish(const float* __rest
   const long b = i / HW, p = i - b * HW;
   const int y = (int)(p / W), x = (int)(p - (long)y * W);
   const float* f = feat + b * C * HW;
-  const float* al = f + 3 * HW;
-  bool m = al[p] > 0.5f;
-  if (y > 0) m = m && al[p - W] > 0.5f;
-  if (y < H - 1) m = m && al[p + W] > 0.5f;
-  if (x > 0) m = m && al[p - 1] > 0.5f;
-  if (x < W - 1) m = m && al[p + 1] > 0.5f;
-  const float mf = m ? 1.f : 0.f;
-  for (int c = 0; c < 3; ++c) {
-    float v = fminf(fmaxf(f[c * HW + p] / 255.f, 0.f), 1.f);
-    v = 255.f * fminf(fmaxf(v * mf, 0.f), 1.f);
-    out[i * 3 + c] = (unsigned char)(int)v;
-  }
+  const float* al = f + 3 * HW + p;
+  const float mf = vv_disk1(y, x, H, W, [&](int d) { return al[d] > 0.5f; }) ? 1.f : 0.f;
+  for (int c = 0; c < 3; ++c) out[i * 3 + c] = (unsigned char)vv_byte(f[c * HW + p], mf);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The virtual views of many frames in one pass (dyn_vv_frames): batch entry b = f * V + v of the splat reads frame f = b / V, so no frame is
-// copied V times.  The arithmetic of every value is that of k_sobel_alpha, k_splat_project, k_splat_resolve<true> and k_vv_finish above,
-// operation for operation, and the sums run in the same ascending contribution id: the bytes equal the per-frame chain's.
+// copied V times.  Every value comes from the bodies the per-frame chain runs (sobel_alpha, k_splat_project<>, splat_walk, vv_byte,
+// vv_disk1) and the sums run in the same ascending contribution id: the bytes equal the per-frame chain's.
 //
-//   k_vv_source    grid (cdiv(HW, 256), F): per frame pixel the splat's source (255 r, 255 g, 255 b, alpha) as one float4,
-//                  alpha = exp(-0.5 |sobel((1 / disp) / 10)|) with the nine taps recomputed from disp (replicate border)
-//   k_vv_project   k_splat_project with depth = 1 / disp[f] and the intrinsics of frame f
-//   k_vv_resolve   grid (cdiv(HW, 256), B): the four channels the epilogue reads (the splatted importance and ones channels feed nothing) and
-//                  the first half of the epilogue: one dword per view pixel, bytes 0..2 = uint8(255 clip(rgb / 255, 0, 1)), byte 3 = alpha > 0.5
-//   k_vv_erode     the disk(1) erosion of byte 3 (out-of-image neighbours do not erode) and the masked rgb bytes: the values are in 0..1
-//                  and the mask is 0 or 1, so clip(v * m, 0, 1) is v or 0 and the byte is the resolved one or 0
+//   k_vv_source            grid (cdiv(HW, 256), F): per frame pixel the splat's source (255 r, 255 g, 255 b, alpha) as one float4,
+//                          alpha = sobel_alpha of (1 / disp) / 10 at beta = 0.5, the nine taps recomputed from disp
+//   k_splat_project<true>  depth = 1 / disp and the intrinsics of frame b / V
+//   k_vv_resolve           grid (cdiv(HW, 256), B): splat_walk over the four channels the epilogue reads (the splatted importance and ones
+//                          channels feed nothing) and the first half of the epilogue: one dword per view pixel, bytes 0..2 = vv_byte of
+//                          r, g, b unmasked, byte 3 = alpha > 0.5
+//   k_vv_erode             vv_disk1 of byte 3 and the masked rgb bytes: the values are in 0..1 and the mask is 0 or 1, so clip(v * m, 0, 1)
+//                          is v or 0 and the byte is the resolved one or 0
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (1 / disp) / 10 as torch forms it for a tensor on the device it runs on: a HIP tensor over a host scalar is multiplied by the fp32
 // reciprocal of the scalar, a host tensor is divided
@@ -405,110 +440,40 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_vv_source(const float* __rest
   const long f = blockIdx.y;
   const int y = (int)(p / W), xx = (int)(p - (long)y * W);
   const float* d = disp + f * HW;
-  const int ym = y > 0 ? y - 1 : 0, yp = y < H - 1 ? y + 1 : H - 1;
-  const int xm = xx > 0 ? xx - 1 : 0, xp = xx < W - 1 ? xx + 1 : W - 1;
-  auto v = [&](int yy, int x2) { return vv_tenth(1.f / d[(long)yy * W + x2], by_division); };
-  const float gx = ((v(ym, xp) - v(ym, xm)) + 2.f * (v(y, xp) - v(y, xm))) + (v(yp, xp) - v(yp, xm));
-  const float gy = ((v(yp, xm) - v(ym, xm)) + 2.f * (v(yp, xx) - v(ym, xx))) + (v(yp, xp) - v(ym, xp));
   const float* c = img + (f * HW + p) * 3;
   float4 o;
   o.x = c[0] * 255.f;
   o.y = c[1] * 255.f;
   o.z = c[2] * 255.f;
-  o.w = expf(-0.5f * sqrtf(gx * gx + gy * gy));
+  o.w = sobel_alpha(y, xx, H, W, 0.5f, [&](int yy, int x2) { return vv_tenth(1.f / d[(long)yy * W + x2], by_division); });
   rgba[f * HW + p] = o;
 }
 
-// grid (<= SPLAT_PROJECT_BLOCKS, B): as k_splat_project
-__global__ __launch_bounds__(SPLAT_THREADS) void k_vv_project(const float* __restrict__ disp, const float* __restrict__ kinv,
-                                                              const float* __restrict__ rot, const float* __restrict__ kdst,
-                                                              const float* __restrict__ tr, int H, int W, int V, float* __restrict__ flow,
-                                                              float* __restrict__ imp, unsigned* __restrict__ minmax) {
-  const int b = blockIdx.y, f = b / V;
-  const long HW = (long)H * W;
-  const float* Ki = kinv + f * 9;
-  const float* Rm = rot + b * 9;
-  const float* Kd = kdst + f * 9;
-  const float* tv = tr + b * 3;
-  float hi = -INFINITY, nlo = -INFINITY;
-  for (long p = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x; p < HW; p += (long)gridDim.x * SPLAT_THREADS) {
-    const int y = (int)(p / W), x = (int)(p - (long)y * W);
-    const float xf = (float)x, yf = (float)y, d = 1.f / disp[f * HW + p];
-    float P[3], S[3], Q[3];
-    for (int i = 0; i < 3; ++i) P[i] = ((d * Ki[i * 3]) * xf + (d * Ki[i * 3 + 1]) * yf) + (d * Ki[i * 3 + 2]);
-    for (int i = 0; i < 3; ++i) S[i] = ((Rm[i * 3] * P[0] + Rm[i * 3 + 1] * P[1]) + Rm[i * 3 + 2] * P[2]) + tv[i];
-    for (int i = 0; i < 3; ++i) Q[i] = (Kd[i * 3] * S[0] + Kd[i * 3 + 1] * S[1]) + Kd[i * 3 + 2] * S[2];
-    const float zc = Q[2] < 1e-8f ? 1e-8f : Q[2];
-    flow[(b * 2) * HW + p] = Q[0] / zc - xf;
-    flow[(b * 2 + 1) * HW + p] = Q[1] / zc - yf;
-    const float im = 1.f / Q[2];
-    imp[b * HW + p] = im;
-    hi = fmaxf(hi, im);
-    nlo = fmaxf(nlo, -im);
-  }
-  hi = wave_max(hi);
-  nlo = wave_max(nlo);
-  float* red = reinterpret_cast<float*>(dyn_smem);  // [2][waves]
-  constexpr int NW = SPLAT_THREADS / DYN_WAVE;
-  if (dyn_lane() == 0) {
-    red[dyn_wave()] = hi;
-    red[NW + dyn_wave()] = nlo;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < NW; ++w) {
-      hi = fmaxf(hi, red[w]);
-      nlo = fmaxf(nlo, red[NW + w]);
-    }
-    atomicMax(&minmax[2 * b], splat_ord(hi));
-    atomicMax(&minmax[2 * b + 1], splat_ord(nlo));
-  }
-}
-
 struct VvResolveArgs {
-  int H, W, V;
+  SplatLists l;
+  int V;
   const float4* rgba;   // [F,H,W] (r, g, b, alpha)
-  const float* flow;    // [B,2,H,W]
-  const float* mult;    // [B,H,W]
-  float eps;
-  const unsigned* ids;
-  const int* start;
-  const int* end;
   unsigned* pix;        // [B,H,W]
 };
 
-__device__ __forceinline__ unsigned vv_byte(float feat) {
-  float v = fminf(fmaxf(feat / 255.f, 0.f), 1.f);
-  v = 255.f * fminf(fmaxf(v * 1.f, 0.f), 1.f);
-  return (unsigned)(int)v;
-}
-
 __global__ __launch_bounds__(SPLAT_THREADS) void k_vv_resolve(VvResolveArgs a) {
   const int b = blockIdx.y;
-  const long HW = (long)a.H * a.W;
+  const long HW = (long)a.l.H * a.l.W;
   const long p = (long)blockIdx.x * SPLAT_THREADS + threadIdx.x;
   if (p >= HW) return;
   const long i = b * HW + p;
   const float4* frame = a.rgba + (long)(b / a.V) * HW;
   float n0 = 0.f, n1 = 0.f, n2 = 0.f, n3 = 0.f, den = 0.f;
-  const int s = a.start[i], e = a.end[i];
-  for (int k = s; k < e; ++k) {
-    const unsigned id = a.ids[k];
-    const long src = (long)(id >> 2);
-    const long sp = src - b * HW;
-    const int sy = (int)(sp / a.W), sx = (int)(sp - (long)sy * a.W);
-    const SplatTap t = splat_tap(sx, sy, a.flow[(b * 2) * HW + sp], a.flow[(b * 2 + 1) * HW + sp], a.H, a.W);
-    const float w = splat_corner_weight(t, (int)(id & 3u));
-    const float m = a.mult[src];
+  splat_walk(a.l, b, i, [&](float w, float m, long, long sp) {
     const float4 f = frame[sp];
     n0 += w * (f.x * m);
     n1 += w * (f.y * m);
     n2 += w * (f.z * m);
     n3 += w * (f.w * m);
     den += w * m;
-  }
-  const float d = den + a.eps;
-  a.pix[i] = vv_byte(n0 / d) | (vv_byte(n1 / d) << 8) | (vv_byte(n2 / d) << 16) | ((n3 / d > 0.5f ? 1u : 0u) << 24);
+  });
+  const float d = den + a.l.eps;
+  a.pix[i] = vv_byte(n0 / d, 1.f) | (vv_byte(n1 / d, 1.f) << 8) | (vv_byte(n2 / d, 1.f) << 16) | ((n3 / d > 0.5f ? 1u : 0u) << 24);
 }
 
 // n = B * H * W view pixels; view b goes to out + b * pitch
@@ -520,11 +485,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_vv_erode(const unsigned* __re
   const long b = i / HW, p = i - b * HW;
   const int y = (int)(p / W), x = (int)(p - (long)y * W);
   const unsigned v = pix[i];
-  bool m = (v >> 24) != 0u;
-  if (y > 0) m = m && (pix[i - W] >> 24) != 0u;
-  if (y < H - 1) m = m && (pix[i + W] >> 24) != 0u;
-  if (x > 0) m = m && (pix[i - 1] >> 24) != 0u;
-  if (x < W - 1) m = m && (pix[i + 1] >> 24) != 0u;
+  const bool m = vv_disk1(y, x, H, W, [&](int d) { return (pix[i + d] >> 24) != 0u; });
   unsigned char* o = out + b * pitch + p * 3;
   for (int c = 0; c < 3; ++c) o[c] = m ? (unsigned char)(v >> (8 * c)) : (unsigned char)0;
 }
@@ -597,14 +558,47 @@ static int splat_sort(const SplatLayout& L, char* ws, unsigned** ids, hipStream_
   return 0;
 }
 
+// The refusals every entry point ends its checks with: the workspace (on 16 bytes where float4 are kept in it), then a NaN eps.  (The
+// shape refusal stays with the entry: its text names the entry's own sizes, and the entry's pointer checks come between the two.)
+static int splat_admit(const char* who, const void* ws, size_t given, size_t need, bool on16, bool eps_ok) {
+  DYN_REQUIRE(ws && given >= need && (!on16 || ((uintptr_t)ws & 15) == 0), "%s: workspace of %zu bytes given, %zu needed%s", who, given, need,
+              on16 ? ", on 16 bytes" : "");
+  DYN_REQUIRE(eps_ok, "%s: eps is NaN", who);
+  return 0;
+}
+
+// The front half of a forward splat: clear min / max, k_splat_project, k_splat_keys, the sort.  Returns the sorted ids through *ids.
+// B batch entries of which V share a depth plane and intrinsics (k_splat_project); recip: the planes hold disparities.
+static int splat_project_sort(const char* who, const SplatLayout& L, char* ws, int B, int H, int W, int V, bool recip, const float* depth,
+                              const float* kinv, const float* rot, const float* kdst, const float* tr, float* flow, float* imp, float* mult,
+                              unsigned** ids, hipStream_t st) {
+  unsigned* minmax = (unsigned*)(ws + L.minmax);
+  if (hipMemsetAsync(minmax, 0, (size_t)B * 2 * 4, st) != hipSuccess) {
+    dyn_set_error("%s: hipMemsetAsync failed", who);
+    return DYN_E_LAUNCH;
+  }
+  const int hwblocks = dyn_cdiv((long)H * W, SPLAT_THREADS);
+  const int pblocks = hwblocks < SPLAT_PROJECT_BLOCKS ? hwblocks : SPLAT_PROJECT_BLOCKS;
+  DYN_LAUNCH(DYN_K_SPLAT_PROJECT, "k_splat_project", (recip ? k_splat_project<true> : k_splat_project<false>), dim3(pblocks, B),
+             dim3(SPLAT_THREADS), 2 * (SPLAT_THREADS / DYN_WAVE) * 4, st, depth, kinv, rot, kdst, tr, H, W, V, flow, imp, minmax);
+  DYN_LAUNCH(DYN_K_SPLAT_KEYS, "k_splat_keys", k_splat_keys, dim3(hwblocks, B), dim3(SPLAT_THREADS), 0, st, (const float*)flow, H, W,
+             (unsigned)L.N, (const float*)imp, (const unsigned*)minmax, mult, (unsigned*)(ws + L.keys0), (int*)(ws + L.start), (int*)(ws + L.end));
+  return splat_sort(L, ws, ids, st);
+}
+
+static SplatLists splat_lists(const SplatLayout& L, const char* ws, int H, int W, const float* flow, const float* mult, float eps,
+                              const unsigned* ids) {
+  return SplatLists{H, W, flow, mult, eps, ids, (const int*)(ws + L.start), (const int*)(ws + L.end)};
+}
+
 extern "C" int dyn_splat(const DynSplatParams* p, void* stream) {
   DYN_REQUIRE(p, "dyn_splat: null params");
   SplatLayout L;
   DYN_REQUIRE(p->C > 0 && splat_layout(p->B, p->H, p->W, L), "dyn_splat: bad shape B=%d C=%d H=%d W=%d (B*H*W <= 2^28)", p->B, p->C, p->H,
               p->W);
   DYN_REQUIRE(p->frame && p->flow && p->out, "dyn_splat: frame, flow and out are required");
-  DYN_REQUIRE(p->workspace && p->workspace_bytes >= L.total, "dyn_splat: workspace of %zu bytes given, %zu needed", p->workspace_bytes, L.total);
-  DYN_REQUIRE(!p->normalize || p->eps == p->eps, "dyn_splat: eps is NaN");
+  int rc = splat_admit("dyn_splat", p->workspace, p->workspace_bytes, L.total, false, !p->normalize || p->eps == p->eps);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)p->workspace;
   const long HW = (long)p->H * p->W;
@@ -612,13 +606,11 @@ extern "C" int dyn_splat(const DynSplatParams* p, void* stream) {
              p->H, p->W, (unsigned)L.N, (const float*)nullptr, (const unsigned*)nullptr, (float*)nullptr, (unsigned*)(ws + L.keys0),
              (int*)(ws + L.start), (int*)(ws + L.end));
   unsigned* ids = nullptr;
-  int rc = splat_sort(L, ws, &ids, st);
+  rc = splat_sort(L, ws, &ids, st);
   if (rc) return rc;
   SplatResolveArgs a;
-  a.C = p->C; a.H = p->H; a.W = p->W;
-  a.frame = p->frame; a.imp = nullptr; a.flow = p->flow; a.mult = p->multiplier;
-  a.normalize = p->normalize ? 1 : 0; a.eps = p->eps;
-  a.ids = ids; a.start = (const int*)(ws + L.start); a.end = (const int*)(ws + L.end);
+  a.l = splat_lists(L, ws, p->H, p->W, p->flow, p->multiplier, p->eps, ids);
+  a.C = p->C; a.frame = p->frame; a.imp = nullptr; a.normalize = p->normalize ? 1 : 0;
   a.out = p->out; a.disp = nullptr; a.mask = nullptr;
   DYN_LAUNCH(DYN_K_SPLAT_RESOLVE, "k_splat_resolve", k_splat_resolve<false>,
              dim3(dyn_cdiv(HW, SPLAT_THREADS), dyn_cdiv(p->C, SPLAT_GROUP), p->B), dim3(SPLAT_THREADS), 0, st, a);
@@ -632,37 +624,23 @@ extern "C" int dyn_forward_splat(const DynForwardSplatParams* p, void* stream) {
               p->W, p->C);
   DYN_REQUIRE(p->src && p->depth && p->k_src_inv && p->rot && p->k_dst && p->t, "dyn_forward_splat: src, depth, k_src_inv, rot, k_dst and t are required");
   DYN_REQUIRE(p->feat && p->disp, "dyn_forward_splat: feat and disp are required");
-  DYN_REQUIRE(p->workspace && p->workspace_bytes >= L.total, "dyn_forward_splat: workspace of %zu bytes given, %zu needed", p->workspace_bytes,
-              L.total);
-  DYN_REQUIRE(p->eps == p->eps, "dyn_forward_splat: eps is NaN");
+  int rc = splat_admit("dyn_forward_splat", p->workspace, p->workspace_bytes, L.total, false, p->eps == p->eps);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)p->workspace;
-  const long HW = (long)p->H * p->W;
   float* flow = p->flow ? p->flow : (float*)(ws + L.flow);
   float* imp = p->importance ? p->importance : (float*)(ws + L.imp);
   float* mult = p->weight_exp ? p->weight_exp : (float*)(ws + L.mult);
-  unsigned* minmax = (unsigned*)(ws + L.minmax);
-  if (hipMemsetAsync(minmax, 0, (size_t)p->B * 2 * 4, st) != hipSuccess) {
-    dyn_set_error("dyn_forward_splat: hipMemsetAsync failed");
-    return DYN_E_LAUNCH;
-  }
-  const dim3 grid(dyn_cdiv(HW, SPLAT_THREADS), p->B);
-  const int pblocks = dyn_cdiv(HW, SPLAT_THREADS) < SPLAT_PROJECT_BLOCKS ? dyn_cdiv(HW, SPLAT_THREADS) : SPLAT_PROJECT_BLOCKS;
-  DYN_LAUNCH(DYN_K_SPLAT_PROJECT, "k_splat_project", k_splat_project, dim3(pblocks, p->B), dim3(SPLAT_THREADS), 2 * (SPLAT_THREADS / DYN_WAVE) * 4, st, p->depth, p->k_src_inv, p->rot,
-             p->k_dst, p->t, p->H, p->W, flow, imp, minmax);
-  DYN_LAUNCH(DYN_K_SPLAT_KEYS, "k_splat_keys", k_splat_keys, grid, dim3(SPLAT_THREADS), 0, st, (const float*)flow, p->H, p->W, (unsigned)L.N,
-             (const float*)imp, (const unsigned*)minmax, mult, (unsigned*)(ws + L.keys0), (int*)(ws + L.start), (int*)(ws + L.end));
   unsigned* ids = nullptr;
-  int rc = splat_sort(L, ws, &ids, st);
+  rc = splat_project_sort("dyn_forward_splat", L, ws, p->B, p->H, p->W, 1, false, p->depth, p->k_src_inv, p->rot, p->k_dst, p->t, flow, imp,
+                          mult, &ids, st);
   if (rc) return rc;
   SplatResolveArgs a;
-  a.C = p->C; a.H = p->H; a.W = p->W;
-  a.frame = p->src; a.imp = imp; a.flow = flow; a.mult = mult;
-  a.normalize = 1; a.eps = p->eps;
-  a.ids = ids; a.start = (const int*)(ws + L.start); a.end = (const int*)(ws + L.end);
+  a.l = splat_lists(L, ws, p->H, p->W, flow, mult, p->eps, ids);
+  a.C = p->C; a.frame = p->src; a.imp = imp; a.normalize = 1;
   a.out = p->feat; a.disp = p->disp; a.mask = p->mask;
   DYN_LAUNCH(DYN_K_SPLAT_RESOLVE, "k_splat_resolve", k_splat_resolve<true>,
-             dim3(dyn_cdiv(HW, SPLAT_THREADS), dyn_cdiv(p->C + 2, SPLAT_GROUP), p->B), dim3(SPLAT_THREADS), 0, st, a);
+             dim3(dyn_cdiv((long)p->H * p->W, SPLAT_THREADS), dyn_cdiv(p->C + 2, SPLAT_GROUP), p->B), dim3(SPLAT_THREADS), 0, st, a);
   return 0;
 }
 
@@ -720,14 +698,12 @@ extern "C" int dyn_vv_frames(const DynVvFramesParams* p, void* stream) {
   DYN_REQUIRE(p->img && p->disp && p->k && p->k_inv && p->rot && p->t && p->out, "%s: img, disp, k, k_inv, rot, t and out are required", who);
   DYN_REQUIRE(p->out_pitch >= (int64_t)p->H * p->W * 3, "%s: out_pitch=%ld is smaller than a view of %ld bytes", who, (long)p->out_pitch,
               (long)p->H * p->W * 3);
-  DYN_REQUIRE(p->workspace && p->workspace_bytes >= Y.total && ((uintptr_t)p->workspace & 15) == 0,
-              "%s: workspace of %zu bytes given, %zu needed, on 16 bytes", who, p->workspace_bytes, Y.total);
-  DYN_REQUIRE(p->eps == p->eps, "%s: eps is NaN", who);
+  int rc = splat_admit(who, p->workspace, p->workspace_bytes, Y.total, true, p->eps == p->eps);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)p->workspace;
   const long HW = (long)p->H * p->W;
   const int V = p->V, hwblocks = dyn_cdiv(HW, SPLAT_THREADS);
-  const int pblocks = hwblocks < SPLAT_PROJECT_BLOCKS ? hwblocks : SPLAT_PROJECT_BLOCKS;
   float4* rgba = (float4*)(ws + Y.rgba);
   for (int f0 = 0; f0 < p->F; f0 += Y.G) {
     const int G = p->F - f0 < Y.G ? p->F - f0 : Y.G, B = G * V;
@@ -737,24 +713,15 @@ extern "C" int dyn_vv_frames(const DynVvFramesParams* p, void* stream) {
     float* flow = (float*)(ws + L.flow);
     float* imp = (float*)(ws + L.imp);
     float* mult = (float*)(ws + L.mult);
-    unsigned* minmax = (unsigned*)(ws + L.minmax);
-    if (hipMemsetAsync(minmax, 0, (size_t)B * 2 * 4, st) != hipSuccess) {
-      dyn_set_error("%s: hipMemsetAsync failed", who);
-      return DYN_E_LAUNCH;
-    }
     DYN_LAUNCH(DYN_K_SOBEL_ALPHA, "k_vv_source", k_vv_source, dim3(hwblocks, G), dim3(SPLAT_THREADS), 0, st, p->img + (long)f0 * HW * 3, disp, p->H,
                p->W, p->tenth_by_division ? 1 : 0, rgba);
-    DYN_LAUNCH(DYN_K_SPLAT_PROJECT, "k_vv_project", k_vv_project, dim3(pblocks, B), dim3(SPLAT_THREADS), 2 * (SPLAT_THREADS / DYN_WAVE) * 4, st,
-               disp, p->k_inv + (long)f0 * 9, p->rot + (long)f0 * V * 9, p->k + (long)f0 * 9, p->t + (long)f0 * V * 3, p->H, p->W, V, flow, imp, minmax);
-    DYN_LAUNCH(DYN_K_SPLAT_KEYS, "k_splat_keys", k_splat_keys, dim3(hwblocks, B), dim3(SPLAT_THREADS), 0, st, (const float*)flow, p->H, p->W,
-               (unsigned)L.N, (const float*)imp, (const unsigned*)minmax, mult, (unsigned*)(ws + L.keys0), (int*)(ws + L.start), (int*)(ws + L.end));
     unsigned* ids = nullptr;
-    int rc = splat_sort(L, ws, &ids, st);
+    rc = splat_project_sort(who, L, ws, B, p->H, p->W, V, true, disp, p->k_inv + (long)f0 * 9, p->rot + (long)f0 * V * 9, p->k + (long)f0 * 9,
+                            p->t + (long)f0 * V * 3, flow, imp, mult, &ids, st);
     if (rc) return rc;
     VvResolveArgs a;
-    a.H = p->H; a.W = p->W; a.V = V;
-    a.rgba = rgba; a.flow = flow; a.mult = mult; a.eps = p->eps;
-    a.ids = ids; a.start = (const int*)(ws + L.start); a.end = (const int*)(ws + L.end);
+    a.l = splat_lists(L, ws, p->H, p->W, flow, mult, p->eps, ids);
+    a.V = V; a.rgba = rgba;
     a.pix = (unsigned*)imp;  // the importance was consumed by k_splat_keys: its plane holds the resolved pixels
     DYN_LAUNCH(DYN_K_SPLAT_RESOLVE, "k_vv_resolve", k_vv_resolve, dim3(hwblocks, B), dim3(SPLAT_THREADS), 0, st, a);
     DYN_LAUNCH(DYN_K_VV_FINISH, "k_vv_erode", k_vv_erode, dim3(dyn_cdiv(L.N, SPLAT_THREADS)), dim3(SPLAT_THREADS), 0, st, (const unsigned*)a.pix,

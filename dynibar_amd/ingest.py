@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import virtual_views as vvmod
 from ._lib import call, stream_of
 
 MAX_RADIUS = 15
@@ -496,19 +497,7 @@ def _upload(a, dev):
   return t.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else t
 
 
-def relative_transforms(c2w, vv_c2w):
-  """``inv([vv_c2w; 0 0 0 1]) @ c2w`` for every frame and view in float64 on the host, as ``virtual_views.frame_batch`` forms them
-  (render_source_vv.py:297-305): c2w ``[N, 4, 4]``, vv_c2w ``[N, V, 3, 4]`` -> (rot float64 ``[N, V, 3, 3]``, t float64 ``[N, V, 3]``)."""
-  N, V = len(vv_c2w), len(vv_c2w[0])
-  rot, tr = np.empty((N, V, 3, 3)), np.empty((N, V, 3))
-  for i in range(N):
-    ref = np.asarray(c2w[i], dtype=np.float64)
-    for k in range(V):
-      tgt = np.eye(4)
-      tgt[:3, :4] = vv_c2w[i][k]
-      T = np.dot(np.linalg.inv(tgt), ref)
-      rot[i, k], tr[i, k] = T[:3, :3], T[:3, 3]
-  return rot, tr
+relative_transforms = vvmod.relative_transforms  # the pose algebra virtual_views.frame_batch uses
 
 
 def virtual_views(images01, disp, K, c2w, vv_c2w, out=None, batch=DEFAULT_BATCH, device=None):
@@ -574,7 +563,6 @@ def build_virtual_views(net_images, depth, intrinsics_t, cam_c2w, size, batch=DE
   -> (views uint8 ``[N, 8, H, W, 3]`` on the device, source_vv_poses float32 ``[8, 3, 4, N]`` on the host: the array the script saves).
   The 5th depth percentiles come from ``depth_bounds`` (one copy of N floats to the host, which the float64 pose algebra needs); the frame is
   resized with ``resize_area_f32``, ``1 / depth`` with ``resize_linear`` (reciprocal first, as the script has it)."""
-  from . import virtual_views as vvmod
   dev = _device(device, net_images, depth, out)
   img = _tensor(net_images, 'net_images', (torch.float32,), dev)
   dep = _tensor(depth, 'depth', (torch.float32,), dev)
@@ -664,10 +652,8 @@ def _depth_record(path):
   """one ``--cvd_dir`` file -> (source frame index, depth float32 [h, w], transposed intrinsics [3, 3], camera-to-world [4, 4], (w, h) of the
   network's image).  The frame index is the four digits after the file name's five-letter prefix."""
   import os
-  with np.load(path) as z:
-    net_h, net_w = z['img_1'].shape[-2:]
-    return (int(os.path.basename(path)[5:9]), np.ascontiguousarray(z['depth'][0, 0], dtype=np.float32), z['K'][0, 0, 0], z['cam_c2w'][0],
-            (int(net_w), int(net_h)))
+  img, depth, Kt, c2w = vvmod.read_record(path)
+  return int(os.path.basename(path)[5:9]), np.ascontiguousarray(depth, dtype=np.float32), Kt, c2w, (int(img.shape[1]), int(img.shape[0]))
 
 
 def main(argv=None):
@@ -724,26 +710,14 @@ def write_virtual_views(records, dense, size, batch=DEFAULT_BATCH, device=None):
   """The files of render_source_vv.py from the ``*.npz`` depth records, under ``dense``: ``source_virtual_views_WxH/NNNNN/KK.png`` and
   ``source_vv_poses.npy`` -> the list of the PNG paths, in the order ``virtual_views.main`` reports them."""
   import os
-
-  from PIL import Image
-  net, depth, Kt, cams = [], [], [], []
-  for path in records:
-    with np.load(path) as z:
-      net.append(np.ascontiguousarray(z['img_1'][0].transpose(1, 2, 0), dtype=np.float32))
-      depth.append(np.ascontiguousarray(z['depth'][0, 0], dtype=np.float32))
-      Kt.append(z['K'][0, 0, 0])
-      cams.append(z['cam_c2w'][0])
-  views, poses = build_virtual_views(np.stack(net), np.stack(depth), np.stack(Kt), cams, size, batch=batch, device=device)
+  net, depth, Kt, cams = zip(*(vvmod.read_record(path) for path in records))
+  f32 = lambda xs: np.stack([np.ascontiguousarray(x, dtype=np.float32) for x in xs])
+  views, poses = build_virtual_views(f32(net), f32(depth), np.stack(Kt), list(cams), size, batch=batch, device=device)
   np.save(os.path.join(dense, 'source_vv_poses.npy'), poses)
   save_dir = os.path.join(dense, 'source_virtual_views_%dx%d' % size)
   written = []
   for i in range(len(records)):
-    sub = os.path.join(save_dir, '%05d' % i)
-    os.makedirs(sub, exist_ok=True)
-    frame = views[i].cpu().numpy()
-    for k in range(frame.shape[0]):
-      written.append(os.path.join(sub, '%02d.png' % k))
-      Image.fromarray(frame[k]).save(written[-1])
+    written += vvmod.write_frame_views(save_dir, i, views[i].cpu().numpy())
   return written
 
 

@@ -11,6 +11,8 @@ this module writes them.
   * ``virtual_view_poses``    -- the pose selection and the two axis switches of :195-251;
   * ``sobel_fg_alpha``        -- :118-128 (k_sobel_alpha);
   * ``render_frame_virtual_views`` -- the 8 views of one frame (:253-330) in one batched forward splat and one k_vv_finish;
+  * ``relative_transforms``, ``read_record``, ``write_frame_views`` -- the pose algebra, the ``.npz`` decoding and the PNG tree, stated here
+                                 once for this module and ``dynibar_amd.ingest``;
   * ``main``                  -- the script: same inputs, same output tree and file names.
 
 Resizing to the working size uses ``torch.nn.functional.interpolate`` (nearest / area / bilinear, ``align_corners=False``) where the
@@ -137,6 +139,21 @@ def virtual_view_poses(c2w_mats, bounds, hwf):
   return vv_poses_final, c2w_mats_vsv
 
 
+def relative_transforms(c2w, vv_c2w):
+  """``inv([vv_c2w; 0 0 0 1]) @ c2w`` for every frame and view in float64 on the host (render_source_vv.py:297-305): c2w ``[N, 4, 4]``,
+  vv_c2w ``[N, V, 3, 4]`` -> (rot float64 ``[N, V, 3, 3]``, t float64 ``[N, V, 3]``)."""
+  N, V = len(vv_c2w), len(vv_c2w[0])
+  rot, tr = np.empty((N, V, 3, 3)), np.empty((N, V, 3))
+  for i in range(N):
+    ref = np.asarray(c2w[i], dtype=np.float64)
+    for k in range(V):
+      tgt = np.eye(4)
+      tgt[:3, :4] = vv_c2w[i][k]
+      T = np.dot(np.linalg.inv(tgt), ref)
+      rot[i, k], tr[i, k] = T[:3, :3], T[:3, 3]
+  return rot, tr
+
+
 def frame_batch(img, disp, K, c2w_ref, vv_c2w):
   """The B = len(vv_c2w) forward-splat inputs of one frame (render_source_vv.py:283-307), on the device: (src [B,H,W,4], depth [B,H,W],
   rot [B,3,3], t [B,3], k [B,3,3]).  img [H,W,3] in [0,1], disp [H,W], K [3,3], c2w_ref [4,4] (float64 poses), vv_c2w [B,3,4]."""
@@ -148,17 +165,11 @@ def frame_batch(img, disp, K, c2w_ref, vv_c2w):
   alpha = sobel_fg_alpha(pred_depth, 'sobel', beta=0.5)[0, 0, ..., None]
   rgba = torch.cat([img * 255.0, alpha], -1)
   B = len(vv_c2w)
-  rot, tr = [], []
-  for k in range(B):
-    cam_tgt2w = np.eye(4)
-    cam_tgt2w[:3, :4] = vv_c2w[k]
-    T = np.dot(np.linalg.inv(cam_tgt2w), np.asarray(c2w_ref, dtype=np.float64))
-    rot.append(T[:3, :3])
-    tr.append(T[:3, 3])
+  rot, tr = relative_transforms([c2w_ref], [vv_c2w])
   src = rgba[None].expand(B, H, W, 4).contiguous()
   depth = (1.0 / disp)[None].expand(B, H, W).contiguous()
   k = torch.from_numpy(np.array(K)).float()[None].expand(B, 3, 3).contiguous()
-  return src, depth, torch.from_numpy(np.stack(rot)).float(), torch.from_numpy(np.stack(tr)).float(), k
+  return src, depth, torch.from_numpy(rot[0]).float(), torch.from_numpy(tr[0]).float(), k
 
 
 def render_frame_virtual_views(img, disp, K, c2w_ref, vv_c2w):
@@ -186,9 +197,31 @@ def _read_image(path):
     return np.asarray(im)
 
 
+def read_record(path):
+  """One ``--cvd_dir`` file as the scripts index it -> (img_1 [h, w, 3] channels last, depth [h, w], the stored transposed K [3, 3],
+  cam_c2w [4, 4]), in the file's dtypes."""
+  with np.load(path) as z:
+    return z['img_1'][0].transpose(1, 2, 0), z['depth'][0, 0], z['K'][0, 0, 0], z['cam_c2w'][0]
+
+
+def _frame_dir(save_dir, i):
+  sub = os.path.join(save_dir, '%05d' % i)
+  os.makedirs(sub, exist_ok=True)
+  return sub
+
+
+def write_frame_views(save_dir, i, views):
+  """The views uint8 [V, H, W, 3] of frame ``i`` -> ``save_dir/NNNNN/KK.png``; returns the paths in view order."""
+  from PIL import Image
+  sub = _frame_dir(save_dir, i)
+  paths = [os.path.join(sub, '%02d.png' % k) for k in range(len(views))]
+  for path, view in zip(paths, views):
+    Image.fromarray(view).save(path)
+  return paths
+
+
 def main(argv=None):
   """render_source_vv.py:134-330 with the same inputs, output tree and file names."""
-  from PIL import Image
   parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
   parser.add_argument('--data_dir', type=str, help='data directory')
   parser.add_argument('--cvd_dir', type=str, help='video depth directory')
@@ -208,12 +241,10 @@ def main(argv=None):
   c2w_mats, bounds_mats = [], []
   K = None
   for path in pt_out_list:
-    pt_data = np.load(path)
-    pred_depth = pt_data['depth'][0, 0, ...]
-    img = pt_data['img_1'][0].transpose(1, 2, 0)
-    c2w_mats.append(pt_data['cam_c2w'][0])
+    img, pred_depth, Kt, cam_c2w = read_record(path)
+    c2w_mats.append(cam_c2w)
     bounds_mats.append(np.percentile(pred_depth, 5))
-    K = pt_data['K'][0, 0, 0, ...].transpose()
+    K = Kt.transpose()
     K[0, :] *= final_w / img.shape[1]
     K[1, :] *= final_h / img.shape[0]
   h, w, fx, fy = final_h, final_w, K[0, 0], K[1, 1]  # (the last frame's intrinsics, as in the reference)
@@ -223,23 +254,16 @@ def main(argv=None):
 
   written = []
   for i, path in enumerate(pt_out_list):
-    save_sub_dir = os.path.join(save_dir, '%05d' % i)
-    os.makedirs(save_sub_dir, exist_ok=True)
-    pt_data = np.load(path)
-    K = pt_data['K'][0, 0, 0, ...].transpose()
-    img = pt_data['img_1'][0].transpose(1, 2, 0)
-    cam_ref2w = pt_data['cam_c2w'][0]
-    pred_disp = 1.0 / pt_data['depth'][0, 0, ...]
+    _frame_dir(save_dir, i)  # (before the first device call: an output tree that cannot be written fails here)
+    img, pred_depth, Kt, cam_ref2w = read_record(path)
+    K = Kt.transpose()
+    pred_disp = 1.0 / pred_depth
     K[0, :] *= final_w / img.shape[1]
     K[1, :] *= final_h / img.shape[0]
     assert abs(K[0, 0] - K[1, 1]) / abs(K[0, 0] + K[1, 1]) < 0.005
     img = _resize(img, final_h, final_w, 'area')
     pred_disp = _resize(pred_disp, final_h, final_w, 'bilinear')
-    views = render_frame_virtual_views(img, pred_disp, K, cam_ref2w, c2w_mats_vsv[i])
-    for k in range(views.shape[0]):
-      out = os.path.join(save_sub_dir, '%02d.png' % k)
-      Image.fromarray(views[k]).save(out)
-      written.append(out)
+    written += write_frame_views(save_dir, i, render_frame_virtual_views(img, pred_disp, K, cam_ref2w, c2w_mats_vsv[i]))
   return written
 
 

@@ -26,6 +26,14 @@ def test_virtual_views_equal_the_per_frame_path(emu):
   vc.check_views_equal_the_per_frame_path(emu)
 
 
+def test_virtual_views_with_per_frame_intrinsics_that_differ(emu):
+  vc.check_per_frame_intrinsics_that_differ(emu)
+
+
+def test_virtual_views_in_more_than_one_sort_group(emu):
+  vc.check_more_than_one_sort_group(emu)
+
+
 def test_virtual_views_one_frame_one_view(emu):
   vc.check_one_frame_one_view(emu)
 

@@ -33,6 +33,14 @@ def test_virtual_views_equal_the_per_frame_path():
   vc.check_views_equal_the_per_frame_path(DEV)
 
 
+def test_virtual_views_with_per_frame_intrinsics_that_differ():
+  vc.check_per_frame_intrinsics_that_differ(DEV)
+
+
+def test_virtual_views_in_more_than_one_sort_group():
+  vc.check_more_than_one_sort_group(DEV)
+
+
 def test_virtual_views_one_frame_one_view():
   vc.check_one_frame_one_view(DEV)
 

@@ -70,3 +70,21 @@ def test_relative_transforms_are_frame_batchs():
   # the poses of the shared inputs move every view by a few pixels at most: 63 * bound / depth = 4 px at the nearest pixel
   assert 0 < np.abs(tr).max() * K[0, 0] * float(disp.max()) < 6.0
 
+
+def test_relative_transforms_against_the_inverse_written_out():
+  """ingest.relative_transforms and virtual_views.frame_batch share one statement of the pose algebra; this one is the test's own:
+  inv([vv_c2w; 0 0 0 1]) @ c2w in float64 for every frame and view, exact.  float32 poses are promoted before the product, not after."""
+  from dynibar_amd import ingest
+  _, _, _, c2w, vsv = vc.vv_inputs()
+  c2w = c2w.copy()
+  c2w[:, :3, :3] = np.array([[0.36, 0.48, -0.8], [-0.8, 0.6, 0.0], [0.48, 0.64, 0.6]])  # a rotation, so that every entry of the product matters
+  for ref in (c2w, c2w.astype(np.float32)):
+    rot, tr = ingest.relative_transforms(ref, vsv)
+    assert rot.dtype == tr.dtype == np.float64
+    for f in range(3):
+      for v in range(8):
+        tgt = np.concatenate([vsv[f, v].astype(np.float64), [[0.0, 0.0, 0.0, 1.0]]])
+        T = np.linalg.inv(tgt) @ ref[f].astype(np.float64)
+        assert np.array_equal(rot[f, v], T[:3, :3]) and np.array_equal(tr[f, v], T[:3, 3]), (f, v)
+  assert np.abs(rot[0, 0] - np.eye(3)).max() > 0.3
+

@@ -213,6 +213,13 @@ def yardstick(img, disp, K, c2w, vsv):
   return np.stack([vv.render_frame_virtual_views(img[f], disp[f], K, c2w[f], vsv[f]) for f in range(len(img))])
 
 
+@functools.lru_cache(maxsize=None)
+def shared_yardstick(dev):
+  """the yardstick of vv_inputs(), rendered once per device for the checks that compare with it; they leave it unchanged"""
+  img, disp, K, c2w, vsv = vv_inputs()
+  return yardstick(ic.dev_t(img, dev), ic.dev_t(disp, dev), K, c2w, vsv)
+
+
 def interior_holes(view):
   """black pixels with rendered pixels on both sides in their row AND in their column: holes inside the rendered region (disocclusions and
   what the erosion took around them), not the band a view's shift empties along the image border"""
@@ -246,7 +253,7 @@ def behind_camera(disp, K, c2w, vsv):
 def check_views_equal_the_per_frame_path(dev):
   from dynibar_amd import ingest
   img, disp, K, c2w, vsv = vv_inputs()
-  want = yardstick(ic.dev_t(img, dev), ic.dev_t(disp, dev), K, c2w, vsv)
+  want = shared_yardstick(dev)
   assert want.shape == VV_SHAPE + (3,) and want.dtype == np.uint8
   assert_not_vacuous(want)
   di, dd = ic.dev_t(img, dev), ic.dev_t(disp, dev)
@@ -269,6 +276,41 @@ def check_views_equal_the_per_frame_path(dev):
   assert ingest.virtual_views(di, dd, K, c2w, vsv, out=view, batch=2) is view
   s = ic.host(store)
   assert np.array_equal(s[:, :n].reshape(want.shape), want) and (s[:, n:] == 0xA5).all()
+
+
+def check_per_frame_intrinsics_that_differ(dev):
+  """every frame with its own focal length and principal point: the batched projection must read K and K^-1 of frame b / V, not of entry b
+  or of frame 0 (three copies of one K, as above, cannot tell)"""
+  from dynibar_amd import ingest, virtual_views as vv
+  img, disp, K, c2w, vsv = vv_inputs()
+  Ks = np.stack([K] * 3)
+  for f, (scale, dx, dy) in enumerate(((0.9, -1.5, 1.0), (1.0, 0.0, 0.0), (1.1, 2.0, -1.25))):
+    Ks[f, 0, 0] *= F32(scale)
+    Ks[f, 1, 1] *= F32(scale)
+    Ks[f, 0, 2] += F32(dx)
+    Ks[f, 1, 2] += F32(dy)
+  di, dd = ic.dev_t(img, dev), ic.dev_t(disp, dev)
+  want = np.stack([vv.render_frame_virtual_views(di[f], dd[f], Ks[f], c2w[f], vsv[f]) for f in range(3)])
+  assert_not_vacuous(want)
+  assert all(int(np.sum(want[f] != shared_yardstick(dev)[f])) > 1000 for f in (0, 2))  # (the intrinsics matter to the bytes)
+  g = ic.host(ingest.virtual_views(di, dd, Ks, c2w, vsv))
+  assert np.array_equal(g, want), [int(np.sum(g[f] != want[f])) for f in range(3)]
+
+
+def check_more_than_one_sort_group(dev):
+  """At 8 views of 24 x 40 a sort group of dyn_vv_frames holds 8 frames, so a call of nine runs the group loop twice, the second time for
+  frame 8 alone at the offsets of f0 = 8.  The nine frames are the three of vv_inputs() in turn: frame 8 is frame 2, whose bytes are neither
+  frame 0's nor frame 1's."""
+  from dynibar_amd import _lib, ingest
+  img, disp, K, c2w, vsv = vv_inputs()
+  want = shared_yardstick(dev)
+  sizes = [int(_lib.lib().dyn_vv_frames_workspace_bytes(F, 8, 24, 40)) for F in (7, 8, 9)]
+  assert sizes[0] < sizes[1] == sizes[2], sizes  # a group is 8 frames
+  assert min(int(np.sum(want[2] != want[f])) for f in (0, 1)) > 21000
+  idx = np.arange(9) % 3
+  got = ingest.virtual_views(ic.dev_t(img[idx], dev), ic.dev_t(disp[idx], dev), K, c2w[idx], vsv[idx], batch=9)
+  g = ic.host(got)
+  assert np.array_equal(g, want[idx]), [int(np.sum(g[i] != want[idx[i]])) for i in range(9)]
 
 
 def check_one_frame_one_view(dev):
