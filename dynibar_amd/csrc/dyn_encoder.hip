@@ -830,3 +830,5 @@ extern "C" int dyn_enc_in_bwd(const float* dy, const float* y, int relu, const f
              reinterpret_cast<float4*>(dres), dgamma, dbeta);
   return 0;
 }
+
+#include "dyn_lpips.h"  // masked LPIPS of the evaluation (AlexNet features on the fp32 matrix pipe): its own kernels and entry points

@@ -43,6 +43,7 @@ static const char* const g_prof_names[DYN_K_COUNT] = {
     "k_resize_area_u8", "k_resize_linear_f32", "k_resize_nearest", "k_erode_disk_u8", "k_percentile_pair",
     "k_grad_sumsq", "k_grad_stats", "k_grad_scale", "k_adam_step_guarded",
     "k_adamx_step", "k_adamx_step_guarded", "k_adam_advance",
+    "k_lpips_prep", "k_lpips_conv", "k_lpips_pool", "k_lpips_tap", "k_lpips_sums", "k_lpips_finish",
     "k_viewlog_ranges", "k_viewlog_flow_max", "k_viewlog_panels"};
 
 static void prof_flush(int slot) {

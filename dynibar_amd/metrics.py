@@ -1,7 +1,7 @@
-"""The metrics of the reference's evaluation loop (eval_nvidia.py:201-247, :380-457) without LPIPS, on the gfx950 kernels.
+"""The metrics of the reference's evaluation loop (eval_nvidia.py:201-247, :380-457) on the gfx950 kernels; LPIPS is dynibar_amd/lpips.py.
 
     from eval_nvidia import calculate_psnr, calculate_ssim   ->   from dynibar_amd.metrics import calculate_psnr, calculate_ssim
-    numbers = nvidia_frame_metrics(ret['outputs_fine_ref']['rgb'], gt_uint8_or_float, dynamic_mask)   # replaces :383-457 (LPIPS aside)
+    numbers = nvidia_frame_metrics(ret['outputs_fine_ref']['rgb'], gt_uint8_or_float, dynamic_mask, lpips=net)   # replaces :383-457
 
 One ``dyn_frame_metrics`` call (csrc/dyn_metrics.h: k_metrics_tile, k_metrics_finish) prepares the frame -- the valid mask
 ``sum(rgb, -1) > 1e-3`` in float32 in numpy's order of addition, ``float32(uint8) / 255``, both images times the mask, all bit-exact against
@@ -219,23 +219,37 @@ def structural_similarity(im1, im2, *, data_range, full=False):
   return (mssim, out['ssim_map'].cpu().numpy()) if full else mssim
 
 
-def nvidia_frame_metrics(pred_rgb, target, dynamic_mask, *, data_range=REFERENCE_DATA_RANGE):
-  """eval_nvidia.py:380-457 without LPIPS for one frame.  pred_rgb float32 ``[H, W, 3]`` (``ret['outputs_fine_ref']['rgb']``), target float32 in
+def nvidia_frame_metrics(pred_rgb, target, dynamic_mask, *, data_range=REFERENCE_DATA_RANGE, lpips=None):
+  """eval_nvidia.py:380-457 for one frame.  pred_rgb float32 ``[H, W, 3]`` (``ret['outputs_fine_ref']['rgb']``), target float32 in
   [0, 1] or uint8 (the resized ground truth before or after ``/ 255``), dynamic_mask ``[H, W, 3]`` or ``[H, W]`` weights (the resized mv_mask).
   Both images are multiplied by the valid mask; the masks valid, dynamic and 1 - dynamic (the static mask is not multiplied by valid: the
   reference does not) are evaluated in one ``dyn_frame_metrics`` call and the nine sums come back in one copy.
-  -> dict of Python floats: psnr, ssim, dynamic_psnr, dynamic_ssim, static_psnr, static_ssim, valid_fraction."""
+  ``lpips``: a ``dynibar_amd.lpips.LPIPS`` network; one ``dyn_lpips_frame`` call then evaluates the same three masks (H, W >= 31) and its table
+  comes back in the same copy.  None: no LPIPS, the numbers and their bits are those of the call without the keyword.
+  -> dict of Python floats: psnr, ssim, dynamic_psnr, dynamic_ssim, static_psnr, static_ssim, valid_fraction, and with a network lpips,
+  dynamic_lpips, static_lpips."""
   _pair(pred_rgb, target)
   dev = _device_of(pred_rgb, target, dynamic_mask)
   a, b = _image(pred_rgb, 'pred_rgb', dev), _image(target, 'target', dev, allow_u8=True)
   H, W = a.shape[0], a.shape[1]
   dyn = _mask(dynamic_mask, 'dynamic_mask', (H, W), dev)
   masks = torch.stack([dyn, 1 - dyn]).contiguous()  # (:444)
-  sums = frame_sums(a, b, masks, data_range=data_range, apply_valid=True, valid_as_mask0=True)['sums']
-  rows = sums.cpu().tolist()  # the one device-to-host copy of the frame
+  if lpips is None:
+    sums = frame_sums(a, b, masks, data_range=data_range, apply_valid=True, valid_as_mask0=True)['sums']
+    rows, taps = sums.cpu().tolist(), None  # the one device-to-host copy of the frame
+  else:
+    both = _scratch(9 + 30, torch.float64, dev)  # [3, 3] of dyn_frame_metrics, then [3, 5, 2] of dyn_lpips_frame: one copy
+    frame_sums(a, b, masks, data_range=data_range, apply_valid=True, valid_as_mask0=True, out=both[:9].view(3, 3))
+    lpips.frame_sums(a, b, masks, apply_valid=True, valid_as_mask0=True, out=both[9:].view(3, 5, 2))
+    host = both.cpu()  # the one device-to-host copy of the frame
+    rows, taps = host[:9].view(3, 3).tolist(), host[9:].view(3, 5, 2).tolist()
   out = {}
   for name, (sse, ssum, msum) in zip(('', 'dynamic_', 'static_'), rows):
     out[name + 'psnr'] = _psnr_of(sse, msum)
     out[name + 'ssim'] = _ssim_of(ssum, msum)
   out['valid_fraction'] = rows[0][2] / (3 * H * W)
+  if taps is not None:
+    from . import lpips as lpips_mod
+    for name, t in zip(('', 'dynamic_', 'static_'), taps):
+      out[name + 'lpips'] = float(lpips_mod.lpips_of(t))
   return out

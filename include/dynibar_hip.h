@@ -702,6 +702,48 @@ typedef struct {
 } DynFrameMetricsParams;
 int dyn_frame_metrics(const DynFrameMetricsParams* p, double* sums, void* stream);
 
+/* ====== masked LPIPS of the evaluation loop (eval_nvidia.py:250-263 im2tensor, :289-291, :402-457): LPIPS v0.1, net 'alex', 'net-lin' ========
+ * One call evaluates M masks (1..8) on one frame; the features are computed once for all of them.
+ *   1. Preparation as dyn_frame_metrics (valid, float(u8) / 255.0f, both images times valid with apply_valid), then x / 0.5f - 1.0f and the
+ *      scaling layer (x - shift) / scale, shift (-.030, -.088, -.188), scale (.458, .448, .450): fp32, bit-exact against numpy.
+ *   2. torchvision's AlexNet `features` (zero padding, bias), tapped after each ReLU: conv 3->64 k11 s4 p2 | max-pool 3 s2, conv 64->192 k5 p2 |
+ *      max-pool 3 s2, conv 192->384 k3 p1 | conv 384->256 k3 p1 | conv 256->256 k3 p1.  fp32 products on the matrix pipe, fp32 accumulate.
+ *   3. Per tap pixel n = f / (sqrt(sum_c f^2) + 1e-10), d_l = sum_c lin_l[c] (n0 - n1)^2, in double.
+ *   4. A mask's channel 0 is resized to each tap by nearest neighbour, src = (dst * n_in) / n_out in integers; S_l = sum d_l m_l, M_l = sum m_l,
+ *      double, fixed order.  lpips = sum_l S_l / M_l is formed by the caller (a tap with M_l = 0 contributes 0).
+ *      NOT VERIFIED: the script's `models` package (NSFF's modified LPIPS) and its masked form were not available; this is the stated form.
+ * No atomics: two calls give the same bits, a mask's sums do not depend on the other masks, identical images give exactly 0.
+ * dyn_lpips_pack: HOST pointers to 15 row-major fp32 tensors: features.{0,3,6,8,10}.{weight,bias} of torchvision's alexnet in that order
+ * (weight, bias, weight, ...), then lin0..lin4 ([64], [192], [384], [256], [256]).  Refused: a NULL tensor, a non-finite element, a negative
+ * lin weight.  blob: HOST, dyn_lpips_blob_floats() floats; upload it 16-byte aligned.
+ * sums [M][5][2] (DEVICE doubles): (S_l, M_l) per mask and tap.  maps (optional, DEVICE): the five d_l maps one after the other,
+ * dyn_lpips_map_doubles(H, W) doubles, tap l being [H_l][W_l] with H_0 = (H - 7) / 4 + 1, H_1 = (H_0 - 3) / 2 + 1, H_2..4 = (H_1 - 3) / 2 + 1.
+ * prepared (optional, DEVICE): [2][H][W][3] fp32, the prepared and scaled pred and target.
+ * Workspace: DEVICE scratch of dyn_lpips_workspace_bytes(H, W, M) bytes, 16-byte aligned (0: unsupported shape -- H or W below 31, the
+ * smallest image for which both max-pools have a full window, H*W*4 >= 2^31, M outside 1..8). */
+size_t dyn_lpips_blob_floats(void);
+int dyn_lpips_pack(const float* const* tensors, float* blob, size_t blob_floats);
+size_t dyn_lpips_workspace_bytes(int H, int W, int M);
+long dyn_lpips_map_doubles(int H, int W);
+typedef struct {
+  int H, W;
+  int M;                     /* masks evaluated (1..8), the valid mask included when valid_as_mask0 is set */
+  const float* blob;         /* DEVICE copy of the packed weights */
+  const float* pred;         /* [H,W,3] */
+  const void* target;        /* [H,W,3] fp32, or uint8 when target_is_u8 is set */
+  int target_is_u8;
+  const float* masks;        /* M - valid_as_mask0 masks of fp32 weights; channel 0 is used; NULL when there is none */
+  long mask_stride;          /* floats from one mask to the next */
+  int mask_channels;         /* 3: [H,W,3]; 1: [H,W] */
+  int apply_valid;           /* multiply both images by valid */
+  int valid_as_mask0;        /* mask 0 is valid itself */
+  double* maps;              /* dyn_lpips_map_doubles(H, W) doubles or NULL */
+  float* prepared;           /* [2][H][W][3] or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+} DynLpipsParams;
+int dyn_lpips_frame(const DynLpipsParams* p, double* sums, void* stream);
+
 /* ====== training batches from a device-resident scene (ibrnet/data_loaders/monocular.py:120-144, :300-425; sample_ray.py:262-331) ==========
  * The scene is uploaded once: frames and virtual views as uint8 images, every image padded to image_stride bytes (a multiple of 16, so
  * that dword loads stay aligned when H*W*3 is not a multiple of 4), the optional source masks as uint8 in the same way, disparity and

@@ -1,7 +1,8 @@
 """The per-view body of the reference's evaluation loop (eval_nvidia.py:305-400) on Balloon1-shaped synthetic data: ray sampler for the
 whole frame, the four feature-encoder passes (coarse + fine nets on the 7 dynamic and the 11 static source images), render_single_image_nvi
-(64 coarse + 64 fine samples, chunk 8192), the pixels to the host and the masked PSNR the script computes there.  SSIM / LPIPS need the
-script's external packages (skimage, the LPIPS network) and stay with the script.  Shared by bench.py (extra.eval_loop) and runnable alone:
+(64 coarse + 64 fine samples, chunk 8192), the pixels to the host and the masked PSNR the script computes there.  SSIM and LPIPS are
+built since (dynibar_amd.metrics, dynibar_amd.lpips; tools/metricsbench.py, tools/lpipsbench.py) and are not part of this measurement.
+Shared by bench.py (extra.eval_loop) and runnable alone:
     python tools/eval_loop.py [views]
 """
 import json
