@@ -44,6 +44,7 @@ static const char* const g_prof_names[DYN_K_COUNT] = {
     "k_grad_sumsq", "k_grad_stats", "k_grad_scale", "k_adam_step_guarded",
     "k_adamx_step", "k_adamx_step_guarded", "k_adam_advance",
     "k_lpips_prep", "k_lpips_conv", "k_lpips_pool", "k_lpips_tap", "k_lpips_sums", "k_lpips_finish",
+    "k_flow_resize", "k_warp_flow", "k_flow_supervision",
     "k_viewlog_ranges", "k_viewlog_flow_max", "k_viewlog_panels"};
 
 static void prof_flush(int slot) {
@@ -1949,4 +1950,5 @@ extern "C" int dyn_plucker_src(const float* pts, int per_view_pts, const float* 
 #include "dyn_eval.h"
 #include "dyn_viewlog.h"
 #include "dyn_ingest.h"
+#include "dyn_flowprep.h"
 #include "dyn_optim.h"

@@ -40,6 +40,7 @@ enum DynKernelSlot {
   DYN_K_GRAD_SUMSQ, DYN_K_GRAD_STATS, DYN_K_GRAD_SCALE, DYN_K_ADAM_STEP_GUARDED,
   DYN_K_ADAMX_STEP, DYN_K_ADAMX_STEP_GUARDED, DYN_K_ADAM_ADVANCE,
   DYN_K_LPIPS_PREP, DYN_K_LPIPS_CONV, DYN_K_LPIPS_POOL, DYN_K_LPIPS_TAP, DYN_K_LPIPS_SUMS, DYN_K_LPIPS_FINISH,
+  DYN_K_FLOW_RESIZE, DYN_K_WARP_FLOW, DYN_K_FLOW_SUPERVISION,
   DYN_K_VIEWLOG_RANGES, DYN_K_VIEWLOG_FLOW_MAX, DYN_K_VIEWLOG_PANELS, DYN_K_COUNT
 };
 void dyn_prof_begin(int slot, hipStream_t stream);

@@ -1127,6 +1127,42 @@ int dyn_erode_disk_u8(int B, int H, int W, int radius, const void* src, void* ds
 int dyn_percentile_pair(int B, int64_t n, const float* x, int64_t stride, const int32_t* rank, const double* weight, int single, void* out,
                         void* stream);
 
+/* ====== flow supervision (flow_utils.py:6-15 and the forward-backward check built on it) =====================================================
+ * From raw optical flow to what a DeviceScene takes as flow_masks, plus the epipolar error of every flow vector under the scene's cameras.
+ * Plain DEVICE pointers, contiguous arrays, nothing is allocated.  The contract is IEEE operations in a stated order: every product and sum
+ * below is rounded on its own (no fused multiply-add), so a numpy restatement reproduces every output bit.  That the subpixel = 32 branch
+ * agrees with cv2.remap (1/32-pixel fixed-point coordinates, the per-tap constant border, rint) is BELIEVED, NOT VERIFIED: cv2 was not
+ * available.  alpha1 and alpha2 are parameters; nothing is claimed about the values any upstream preprocessing script uses.
+ *   dyn_flow_resize       raw flow fp32 [B,Hs,Ws,2] -> [B,Hd,Wd,2]: each channel by the contract of dyn_resize_linear_f32 (no reciprocal, no
+ *                         divisor), then u * (float)((double)Wd / Ws) and v * (float)((double)Hd / Hs), one rounded product each: numpy's
+ *                         flow *= ratio on a float32 array.  Hs == Hd and Ws == Wd: a copy, bit for bit.
+ *   dyn_warp_flow         flow_utils.warp_flow: img fp32 [B,H,W,C], 1 <= C <= 4, flow [B,H,W,2] -> out [B,H,W,C].  In fp32, per pixel
+ *                         (row, col) with flow (u, v): mx = (float)col + u, my = (float)row + v; mx is clamped to [-2, (float)(W + 1)], my to
+ *                         [-2, (float)(H + 1)], NaN becomes -2 (no result with a tap inside the image changes).  subpixel = 32: s = rint(mx *
+ *                         32) (ties to even), ix = s >> 5 (floor), ax = (float)(s & 31) / 32; subpixel = 0: ix = floor(mx), ax = mx - floor(mx);
+ *                         the same in y.  Weights w00 = (1-ax)*(1-ay), w01 = ax*(1-ay), w10 = (1-ax)*ay, w11 = ax*ay; taps t00 = img[iy][ix],
+ *                         t01 = img[iy][ix+1], t10 = img[iy+1][ix], t11 = img[iy+1][ix+1], a tap outside the image is 0 and is not read
+ *                         (BORDER_CONSTANT, per tap); out = ((t00*w00 + t01*w01) + t10*w10) + t11*w11.
+ *   dyn_flow_supervision  one launch over a scene.  flows fp32 [N,6,H,W,2] in the order of the offsets +1, +2, +3, -1, -2, -3.  The partner of
+ *                         frame i, slot j with offset o is frame i + o, slot (j + 3) % 6; the pair is in range iff 0 <= i + o < N.  An
+ *                         out-of-range pair writes mask 0 and epi 0 and casts no vote.  Else, with f the own flow and w the partner's flow
+ *                         plane warped by f (dyn_warp_flow, C = 2), in double from the fp32 values: a = f.u + w.u, b = f.v + w.v,
+ *                         e = sqrt(a*a + b*b), t = alpha1 * (sqrt(f.u*f.u + f.v*f.v) + sqrt(w.u*w.u + w.v*w.v)) + alpha2, mask = e < t
+ *                         (false for NaN: non-finite flow gives 0).  masks uint8 [N,6,H,W].
+ *                         F double [N,6,9] or null: row-major fundamental matrices, x2^T F x1 = 0 for pixel x1 of frame i and its match x2
+ *                         in frame i + o.  epi fp32 [N,6,H,W] or null, the Sampson distance in double: x = col, y = row, x2 = x + (double)u,
+ *                         y2 = y + (double)v, l_k = (F[k][0]*x + F[k][1]*y) + F[k][2], m0 = (F[0][0]*x2 + F[1][0]*y2) + F[2][0],
+ *                         m1 = (F[0][1]*x2 + F[1][1]*y2) + F[2][1], r = (x2*l0 + y2*l1) + l2, den = ((l0*l0 + l1*l1) + m0*m0) + m1*m1,
+ *                         epi = den > 0 ? (float)(|r| / sqrt(den)) : 0; a non-finite own flow gives 0.  motion uint8 [N,H,W] or null:
+ *                         (the number of in-range j with mask_j == 1 and epi_j > epi_thresh) >= min_votes, on the fp32 epi as stored.
+ *                         epi and motion need F.
+ * Refused before a launch, DYN_E_INVALID: N or B below 1, H or W below 1, H * W >= 2^31, C outside 1..4, a subpixel other than 0 or 32, null
+ * or misaligned pointers (flows and F on 8 bytes, the rest on 4), an output that is an input, epi or motion without F, a NaN parameter. */
+int dyn_flow_resize(int B, int Hs, int Ws, int Hd, int Wd, const float* src, float* dst, void* stream);
+int dyn_warp_flow(int B, int H, int W, int C, const float* img, const float* flow, float* out, int subpixel, void* stream);
+int dyn_flow_supervision(int N, int H, int W, const float* flows, const double* F, double alpha1, double alpha2, int subpixel, float epi_thresh,
+                         int min_votes, void* masks, float* epi, void* motion, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
